@@ -14,13 +14,18 @@ One process per GPU (torch.distributed, backend nccl == RCCL).  Data parallel = 
 seq2seq_vc_amd.distributed.OverlappedBackward: every stage of model.dp_plan() is one captured hipGraph, and the all-reduce of
 the gradients a stage has finished is issued (asynchronously, on RCCL's stream) before the next stage's graph is replayed.
 
-Rank 0 prints ONE JSON line, extended with
+Rank 0 prints ONE JSON line.  A plain run measures the headline only: set-up, warm-up, the timed steps, the line.  With --full the
+line is extended with
   "roofline":     the workload's dominant kernel (MFMA GEMM) timed live with HIP events against the bf16 MFMA peak
   "cpu_baseline": the CPU oracle (fp32 restatement of the reference) timed on this box's host cores
-and, at N = 1 with the default workload, two sub-objects measured in the same run:
+and, at N = 1 with the default workload, sub-objects measured in the same run:
   "aasvc":        configuration C3 (one rank), with its own roofline (4096 x 1536 x 1536 GEMM) and cpu_baseline
   "decode":       configuration C5 (VTN autoregressive decode, 16 utterances, captured step graph): RTF, with the CPU baseline
                   the recipe prescribes (16 single-thread processes, egs/arctic/vc1/run.sh:284-286)
+  "tts", "trainer", "alignment", "memory_bound" (see main())
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32; see dump_outputs()), so that two builds
+can be compared output for output: the inputs, initial weights and dropout seeds are fixed, identical from run to run.
 """
 import argparse
 import json
@@ -495,16 +500,22 @@ class Workload:
         self.opt = FlatAdam(self.model, lr=lr, grad_norm=1.0, warmup_steps=4000, bf16_shadow=(dtype == torch.bfloat16))
         self.loss_buf = torch.zeros(len(self.loss_names), device=dev)
         self.params_m = sum(p.numel() for p in self.model.parameters()) / 1e6
+        self.keep_outputs = False       # --dump-outputs: hold the model outputs of the forward pass (a captured graph rewrites them on every replay)
+        self.outputs = {}
 
     def forward(self, staged=True):
         """One forward pass -> the loss split by the keys of model.dp_plan() (their sum is the training loss); staged=False: one key."""
         from seq2seq_vc_amd.ops import kernels as K
         if self.name in ("vtn", "tts"):
             after, before, logits, ys_, labels_, olens_, _ = self.model(self.xs, self.ilens, self.ys, self.labels, self.olens)
+            if self.keep_outputs:
+                self.outputs = {"after_outs": after.detach(), "before_outs": before.detach(), "logits": logits.detach()}
             l1, bce = self.crit(after, before, logits, ys_, labels_, olens_)
             K.scalars_axpy([(l1.detach(), 1.0), (bce.detach(), 1.0)], self.loss_buf, beta=0.0)     # (logging: one launch of the library)
             return {"loss": self.Fn.weighted_sum([(l1, 1.0), (bce, 1.0)])}
         ret = self.model(self.xs, self.ilens, self.ys, self.olens, self.xs, dp_lengths=self.ilens)
+        if self.keep_outputs:
+            self.outputs = {k: ret[k].detach() for k in ("after_outs", "before_outs", "ds", "log_p_attn") if ret.get(k) is not None}
         l1 = self.l1(ret["after_outs"], ret["before_outs"], ret["ys"], ret["olens"])
         fs = self.fs(ret["log_p_attn"], ret["ilens"], ret["olens_reduced"])
         dur = ret["dur_nll"]          # (B,): summed inside the launches below
@@ -739,6 +750,44 @@ def step_mfma(workload, ms):
         return None
     gf = FWD_BWD_GFLOP[workload]
     return {"gflop_per_step_per_gpu": gf, "achieved_tflops_per_gpu": gf / ms, "frac_of_bf16_peak": gf / ms / BF16_MFMA_PEAK_TFLOPS}
+
+
+DUMP_MAX_ELEMS = 1 << 21        # per array (8 MB of float32): params, grads, <= 4 model outputs + two tiny arrays -> < 64 MB per dump
+DUMP_SAMPLE_SEED = 20240531
+
+
+def _dump_sample(t):
+    """t as float32 on the host; above DUMP_MAX_ELEMS a fixed, seeded sample of its flattened elements (sorted indices drawn from a
+    CPU generator seeded by DUMP_SAMPLE_SEED: the same positions in every run, and in every array of the same size)."""
+    t = t.detach()
+    if t.numel() > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(wl, out_dir):
+    """What the last timed step handed back, as out_dir/<name>.npy (float32):
+      losses          the logged loss terms of the step (wl.loss_names order)
+      opt_state       [step, lr, grad_norm, clip_coef] of the fused optimiser after the step
+      params / grads  the flat fp32 master weights after the update and the flat gradient buffer the step filled
+                      (a seeded sample of DUMP_MAX_ELEMS elements, the same positions in both)
+      <model output>  the forward pass's outputs (vtn / tts: after_outs, before_outs, logits; aasvc: after_outs, before_outs, ds,
+                      log_p_attn), sampled the same way above DUMP_MAX_ELEMS elements
+    -> {name: shape} of what was written."""
+    import numpy as np
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrays = {"losses": wl.loss_buf, "opt_state": wl.opt.state, "params": wl.opt.flat_p, "grads": wl.opt.flat_g, **wl.outputs}
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(_dump_sample(t), dtype=np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name], total = list(a.shape), total + a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    return written
 
 
 # =====================================================================================================================
@@ -1171,8 +1220,13 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="utterance pairs per GPU (default: 32 for vtn, 16 for aasvc, 8 for tts)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying hipGraphs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the AAS-VC (C3) and decode (C5) sub-benchmarks")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure the dominant-kernel roofline, the CPU baseline and (N = 1, vtn) the sub-benchmarks "
+                         "(aasvc, tts, decode, trainer, alignment, memory_bound); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed to DIR/<name>.npy (float32, < 64 MB; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N = 1: skip the sub-benchmarks (aasvc, tts, decode, trainer, ...)")
     ap.add_argument("--roofline-only", action="store_true", help="only run the dominant-kernel loop (for rocprofv3)")
     ap.add_argument("--split-backward", action="store_true",
                     help="N = 1: run the staged backward pass of the data-parallel path without collectives")
@@ -1278,6 +1332,7 @@ def main():
         args.grad_payload = (TR.AASVCTrainer if args.workload == "aasvc" else TR.ARVCTrainer).DP_GRAD_PAYLOAD
     if args.dp_decoder_stages:
         wl.model.dp_decoder_stages = args.dp_decoder_stages      # AAS-VC: decoder layers with a stage (= a bucket) of their own
+    wl.keep_outputs = bool(args.dump_outputs) and rank == 0
     def build(stage_mode):
         return build_step(wl, dist, world, staged, args.force_dist, args.grad_payload, not args.no_graph, collective=args.collective,
                           warmup_eager=max(2, args.warmup if args.no_graph else 2), stage_mode=stage_mode, min_bucket_mb=args.min_bucket_mb)
@@ -1303,6 +1358,8 @@ def main():
     probe = info.pop("_probe")
     check = info.pop("_check")
     dt = time_steps(step, args.steps, args.warmup, dist if dp else None, dev)
+    if args.dump_outputs and rank == 0:
+        print(f"[bench] outputs of the last timed step in {args.dump_outputs}: {dump_outputs(wl, args.dump_outputs)}", file=sys.stderr)
     if args.check_exchange:
         info["exchange_check"] = check()
     if args.stage_times:
@@ -1331,12 +1388,13 @@ def main():
             "final_losses": dict(zip(wl.loss_names, losses), grad_norm=stats["grad_norm"], opt_steps=stats["step"]),
             "step_mfma": step_mfma(args.workload, ms),
         }
-        out["roofline"] = dominant_kernel_roofline(dtype, workload="vtn" if args.workload == "tts" else args.workload)
+        if args.full:
+            out["roofline"] = dominant_kernel_roofline(dtype, workload="vtn" if args.workload == "tts" else args.workload)
         single = world == 1 and not args.force_dist
-        if single and not args.no_cpu_baseline:
+        if args.full and single and not args.no_cpu_baseline:
             out["cpu_baseline"] = {"vtn": cpu_baseline_vtn, "aasvc": cpu_baseline_aasvc, "tts": cpu_baseline_tts}[args.workload](wl.cpu_batch)
             out["speedup_vs_cpu_baseline"] = out["value"] / out["cpu_baseline"]["value"]
-        if single and args.workload == "vtn" and not args.no_extras:
+        if args.full and single and args.workload == "vtn" and not args.no_extras:
             del step
             wl.model = wl.opt = None
             torch.cuda.empty_cache()

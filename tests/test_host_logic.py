@@ -517,6 +517,33 @@ def test_bench_line_keeps_c3_c5_scalars_where_the_driver_keeps_them():
     assert keys.index("memory_bound") < keys.index("config") < keys.index("roofline") < keys.index("cpu_baseline") < keys.index("decode_rtf")
 
 
+def test_bench_dump_outputs_is_float32_bounded_and_samples_the_same_positions(tmp_path):
+    """bench.py --dump-outputs: every array float32, a large one replaced by a seeded sample (the same positions from run to run and in
+    params / grads alike), small ones whole, and the dump stays below 64 MB."""
+    import sys
+    from types import SimpleNamespace
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS * 3 + 5
+    flat_p = torch.arange(n, dtype=torch.float32)
+    opt = SimpleNamespace(state=torch.tensor([7.0, 1e-4, 0.5, 1.0]), flat_p=flat_p, flat_g=-flat_p)
+    wl = SimpleNamespace(loss_buf=torch.tensor([0.25, 0.125]), opt=opt,
+                         outputs={"after_outs": torch.ones(2, 3, 4, dtype=torch.bfloat16), "logits": torch.zeros(2, 3)})
+    shapes = bench.dump_outputs(wl, str(tmp_path / "a"))
+    bench.dump_outputs(wl, str(tmp_path / "b"))
+    assert shapes == {"losses": [2], "opt_state": [4], "params": [bench.DUMP_MAX_ELEMS], "grads": [bench.DUMP_MAX_ELEMS],
+                      "after_outs": [2, 3, 4], "logits": [2, 3]}
+    total = 0
+    for name in shapes:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total < 64 << 20
+    p, g = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "a" / "grads.npy")
+    assert np.array_equal(p, -g) and np.all(np.diff(p) >= 0) and p.max() < n and len(np.unique(p)) > bench.DUMP_MAX_ELEMS // 2
+    assert np.array_equal(np.load(tmp_path / "a" / "losses.npy"), np.array([0.25, 0.125], dtype=np.float32))
+
+
 def test_allreduce_grads_promotes_to_the_widest_dtype():
     """mixed-precision parameter lists (first one bf16) must not round fp32 gradients through bf16."""
     from seq2seq_vc_amd.distributed import allreduce_grads_

@@ -19,9 +19,9 @@ prof() {  # prof <dir> <rocprofv3 args...> -- <command...>
 want() { [[ " ${SECTIONS:-all} " == *" all "* || " ${SECTIONS:-all} " == *" $1 "* ]]; }
 
 if want bench; then
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
-python bench.py --workload aasvc > "$OUT/bench_aasvc.json" 2>> "$OUT/bench.err"
-python bench.py --workload tts --no-extras > "$OUT/bench_tts.json" 2>> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --workload aasvc --full > "$OUT/bench_aasvc.json" 2>> "$OUT/bench.err"
+python bench.py --workload tts --full --no-extras > "$OUT/bench_tts.json" 2>> "$OUT/bench.err"
 fi
 if want dp; then
 # the data-parallel step at world size 1: mechanism alone (--split-backward: marks, no collectives) and with the FORCED exchange, per stage mode
