@@ -693,6 +693,44 @@ int s2svc_mel_log_batch(int B, int Tmax, int nb, int nmel, const float* z, const
 int s2svc_ragged_to_padded(int B, int Tmax, int D, const float* ragged, const int64_t* offsets, const float* mean,
                            const float* inv_scale, float* out, float* labels, void* stream);
 
+/* ========================================================================================== */
+/* HiFi-GAN generator, inference (csrc/hifigan.hip).  Channel-last activations (B, T, C) in    */
+/* `dtype`; absent rows: frames t >= vlens[b] * vmul (vlens counts MEL frames, vmul = the      */
+/* product of the upsampling factors so far; vlens = NULL: every frame present) are read as    */
+/* zero by every tap and written as zero.  No element-wise launches: leaky_relu is applied to  */
+/* the A operand on its way into the MFMA (slope 0 = none), everything else in the epilogue.   */
+/* replaces: urhythmic/vocoder.py:87-106 (HifiganGenerator.forward), :195-202 (ResBlock).      */
+/* ========================================================================================== */
+/* input channels per reduction step: the operands below pad C_in up to this multiple */
+int s2svc_hifigan_cin_padded(int C);
+/* Dilated Conv1d, k odd <= 11, dil <= 5, padding (k-1)/2*dil, 1 <= C_in, C_out <= 512 (vocoder.py:56-58 conv_pre, :125-193 convs1 /
+   convs2):  v = conv(leaky_relu(x, slope)) + bias (+ res);  out = (accumulate ? out : 0) + scale * v;  optional tanh.
+   w_op [C_out][k * Cinp] (s2svc_hifigan_fold mode 0).  res / out (B, T, C_out); out may be res. */
+int s2svc_hifigan_conv1d(int dtype, int B, int T, int Cin, int Cout, int k, int dil, const void* x, const void* w_op, const float* bias,
+                         float slope, const void* res, int accumulate, float scale, int act_tanh, void* out, const int32_t* vlens,
+                         int vmul, void* stream);
+/* ConvTranspose1d, stride u, kernel k, padding (k-u)/2 ((k-u) even, k >= u) as one GEMM without scatter or col2im (vocoder.py:61-73
+   ups[i], with the leaky_relu of :94 in front): rows (b, i), i < T_in + ceil(pad/u), columns (p, o), reduction ceil(k/u) * Cinp,
+   column p of row i is stored at frame t = u*i + p - pad of out (B, u*T_in, C_out).  w_op: s2svc_hifigan_fold mode 1.
+   vmul counts the INPUT frames per mel frame. */
+int s2svc_hifigan_tconv1d(int dtype, int B, int Tin, int Cin, int Cout, int k, int u, const void* x, const void* w_op, const float* bias,
+                          float slope, void* out, const int32_t* vlens, int vmul, void* stream);
+/* Output convolution C -> 1 (vocoder.py:103-105: leaky_relu (torch's default slope 0.01), conv_post, tanh), one lane per sample:
+   y (B, T) fp32; y_pre (or NULL) receives the value before tanh; w [k][C] fp32 (s2svc_hifigan_fold mode 2). */
+int s2svc_hifigan_conv_out(int dtype, int B, int T, int C, int k, const void* x, const float* w, const float* bias, float slope,
+                           int act_tanh, float* y, float* y_pre, const int32_t* vlens, int vmul, void* stream);
+/* Input launch: x element (b, t, c) at b*sb + t*st + c*sc (any strides: the reference's (B, C, N) or the collaters' (B, N, C)) ->
+   out (B, T, C) in out_dtype = a[c] * x + b[c] (a, b fp32 [C] or NULL: the two normalisations of vocoder/vocoder.py:50-55 as one
+   map); frames t >= vlens[b] are written as zero whatever the input holds. */
+int s2svc_hifigan_input(int in_dtype, int out_dtype, int B, int T, int C, const void* x, int64_t sb, int64_t st, int64_t sc,
+                        const float* a, const float* b, void* out, const int32_t* vlens, void* stream);
+/* Weight-norm fold (torch.nn.utils.weight_norm at vocoder.py:56-85, 125-193): w = v * (g / ||v||), norm over all dims but 0, v (D0, D1, k)
+   fp32; g = NULL: v is the weight.  Writes w32 (or NULL) in v's layout and the operand w_op (or NULL; ZERO-FILLED by the caller):
+   mode 0 Conv1d (O, C, k) -> [o][j*Cinp + c];  mode 1 ConvTranspose1d (C, O, k) -> [p*O + o][n*Cinp + c] = w[c, o, p + u*n];
+   mode 2 output convolution (1, C, k) -> fp32 [j*C + c]. */
+int s2svc_hifigan_fold(int mode, int D0, int D1, int k, int u, const float* g, const float* v, float* w32, int op_dtype, void* w_op,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

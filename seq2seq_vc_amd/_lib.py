@@ -281,6 +281,13 @@ _SIGS = {
     "s2svc_stft_logmel_fft": [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32,
                               c_i32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp],
     "s2svc_ragged_to_padded": [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "s2svc_hifigan_cin_padded": [c_i32],
+    "s2svc_hifigan_conv1d": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_i32, c_f32, c_i32, c_vp,
+                             c_vp, c_i32, c_vp],
+    "s2svc_hifigan_tconv1d": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp],
+    "s2svc_hifigan_conv_out": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp],
+    "s2svc_hifigan_input": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "s2svc_hifigan_fold": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
 }
 _RET64 = {"s2svc_gemm_wgrad_ws_floats": [c_vp, c_i32], "s2svc_mas_ws_bytes": [c_i32, c_i32, c_i32], "s2svc_forward_sum_ws_bytes": [c_i32, c_i32, c_i32]}
 

@@ -1,0 +1,334 @@
+"""HiFi-GAN generator on the HIP kernels of csrc/hifigan.hip: mel -> waveform, single and batched, inference only.
+
+Drop-in surface of the reference's `seq2seq_vc/urhythmic/vocoder.py` HifiganGenerator (constructor keywords, defaults and
+`state_dict` keys, with and without weight norm) and of `seq2seq_vc/vocoder/vocoder.py` Vocoder.decode.  Every convolution is one
+launch; activation, residual, the MRF sum / average, tanh and the input transposition / normalisation / cast ride in the kernels'
+prologues and epilogues, so a call of the default configuration is 79 launches (`launch_plan()`).  There is no CPU path."""
+import math
+
+import numpy as np
+import torch
+from torch import nn
+
+from ..ops import functional as Fn
+from ..ops import kernels_vocoder as KV
+
+LRELU_SLOPE = 0.1
+POST_SLOPE = 0.01        # vocoder.py:103 applies F.leaky_relu with torch's DEFAULT slope in front of conv_post
+KINDS = ("input", "conv1d", "tconv1d", "conv_out")   # the input launch + the kernel families a call may launch ("fold" runs at load)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# host logic of the transposed convolution as one GEMM (the kernel's addressing, stated once; tests evaluate it with plain torch)
+# ---------------------------------------------------------------------------------------------------------------------------
+def tconv1d_geometry(k, u):
+    """(pad, ntaps) of ConvTranspose1d(kernel k, stride u, padding (k - u) / 2): output length is exactly u * T_in."""
+    if u < 1 or k < u or (k - u) % 2:
+        raise ValueError(f"ConvTranspose1d kernel {k} / stride {u}: needs k >= u and (k - u) even (padding (k - u) / 2)")
+    return (k - u) // 2, -(-k // u)
+
+
+def tconv1d_rows(t_in, k, u):
+    """GEMM rows per utterance: i = 0 .. T_in + ceil(pad / u) - 1 (the last rows hold the tail taps of the last frames)."""
+    pad, _ = tconv1d_geometry(k, u)
+    return t_in + -(-pad // u)
+
+
+def tconv1d_out_frame(i, p, k, u):
+    """Row i, phase p is output frame u * i + p - pad (stored when it lies inside [0, u * T_in))."""
+    return u * i + p - tconv1d_geometry(k, u)[0]
+
+
+def tconv1d_operand(w, u, cin_padded=None):
+    """w (C_in, C_out, k) -> [u * C_out, ntaps * Cp] with element [p * C_out + o][n * Cp + c] = w[c, o, p + u * n] (zero where
+    p + u * n >= k or c >= C_in): row (i, :) of the GEMM reads input frames i - n, n = 0 .. ntaps - 1."""
+    cin, cout, k = w.shape
+    _, ntaps = tconv1d_geometry(k, u)
+    cp = cin if cin_padded is None else cin_padded
+    op = w.new_zeros(u, cout, ntaps, cp)
+    for p in range(u):
+        for n in range(ntaps):
+            if p + u * n < k:
+                op[p, :, n, :cin] = w[:, :, p + u * n].t()
+    return op.reshape(u * cout, ntaps * cp)
+
+
+def stage_lengths(lens, factors):
+    """Frames of every utterance at the input of stage i (i = 0 .. len(factors)): lens * prod(factors[:i])."""
+    out, m = [], 1
+    for f in list(factors) + [None]:
+        out.append([int(n) * m for n in lens])
+        if f is not None:
+            m *= int(f)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# parameters
+# ---------------------------------------------------------------------------------------------------------------------------
+class _WNConv(nn.Module):
+    """Parameters of one weight-normed convolution in either checkpoint form: (bias, weight_g, weight_v) or (bias, weight)."""
+
+    def __init__(self, wshape, nbias, fan_in):
+        super().__init__()
+        self.wshape = tuple(wshape)
+        bound = 1.0 / math.sqrt(fan_in)
+        v = torch.empty(*wshape).uniform_(-bound, bound)
+        self.bias = nn.Parameter(torch.empty(nbias).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        self.weight_v = nn.Parameter(v)
+
+    @property
+    def normed(self):
+        return "weight_v" in self._parameters
+
+    def set_form(self, normed, weight=None):
+        if normed == self.normed and weight is None:
+            return
+        ref = self.bias
+        for name in ("weight_g", "weight_v", "weight"):
+            self._parameters.pop(name, None)
+        if normed:
+            v = torch.zeros(self.wshape, dtype=ref.dtype, device=ref.device) if weight is None else weight
+            self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
+            self.weight_v = nn.Parameter(v)
+        else:
+            self.weight = nn.Parameter(torch.zeros(self.wshape, dtype=ref.dtype, device=ref.device) if weight is None else weight)
+
+
+class ResBlock(nn.Module):
+    def __init__(self, channels, kernel_size=3, dilation=(1, 3, 5)):
+        super().__init__()
+        mk = lambda: _WNConv((channels, channels, kernel_size), channels, channels * kernel_size)   # noqa: E731
+        self.convs1 = nn.ModuleList([mk() for _ in dilation])
+        self.convs2 = nn.ModuleList([mk() for _ in dilation])
+
+
+class HifiganGenerator(nn.Module):
+    """HiFi-GAN generator (reference urhythmic/vocoder.py:23-114), inference only.  x (B, in_channels, N) -> (B, 1, N * prod(factors))."""
+
+    def __init__(self, in_channels=256, resblock_dilation_sizes=((1, 3, 5), (1, 3, 5), (1, 3, 5)), resblock_kernel_sizes=(3, 7, 11),
+                 upsample_kernel_sizes=(20, 16, 4, 4), upsample_channels=512, upsample_factors=(10, 8, 2, 2), sample_rate=16000):
+        super().__init__()
+        if len(upsample_kernel_sizes) != len(upsample_factors) or len(resblock_kernel_sizes) != len(resblock_dilation_sizes):
+            raise ValueError("upsample_kernel_sizes / upsample_factors and resblock_kernel_sizes / resblock_dilation_sizes pair up")
+        for k, u in zip(upsample_kernel_sizes, upsample_factors):
+            tconv1d_geometry(k, u)
+        for k, ds in zip(resblock_kernel_sizes, resblock_dilation_sizes):
+            if k % 2 == 0 or k > 11 or any(d < 1 or d > 5 for d in ds):
+                raise ValueError("ResBlock kernels: odd k <= 11, dilations 1..5 (csrc/hifigan.hip)")
+        if upsample_channels % (2 ** len(upsample_factors)) or not 1 <= in_channels <= 512 or upsample_channels > 512:
+            raise ValueError("upsample_channels must halve cleanly at every stage; channels <= 512")
+        self.in_channels, self.upsample_channels, self.sample_rate = in_channels, upsample_channels, sample_rate
+        self.upsample_factors, self.upsample_kernel_sizes = tuple(upsample_factors), tuple(upsample_kernel_sizes)
+        self.resblock_kernel_sizes = tuple(resblock_kernel_sizes)
+        self.resblock_dilation_sizes = tuple(tuple(d) for d in resblock_dilation_sizes)
+        self.num_kernels, self.num_upsamples = len(resblock_kernel_sizes), len(upsample_factors)
+        self.conv_pre = _WNConv((upsample_channels, in_channels, 5), upsample_channels, in_channels * 5)
+        self.ups = nn.ModuleList()
+        self.resblocks = nn.ModuleList()
+        for i, (u, k) in enumerate(zip(upsample_factors, upsample_kernel_sizes)):
+            cin, cout = upsample_channels // 2 ** i, upsample_channels // 2 ** (i + 1)
+            self.ups.append(_WNConv((cin, cout, k), cout, cout * k))
+        for i in range(self.num_upsamples):
+            ch = upsample_channels // 2 ** (i + 1)
+            for k, d in zip(resblock_kernel_sizes, resblock_dilation_sizes):
+                self.resblocks.append(ResBlock(ch, k, d))
+        self.conv_post = _WNConv((1, ch, 7), 1, ch * 7)
+        self._ops = {}            # compute dtype -> {layer name: (operand, bias fp32)}
+
+    # ---- checkpoint forms -------------------------------------------------------------------------------------------------
+    def _leaves(self):
+        return [(n, m) for n, m in self.named_modules() if isinstance(m, _WNConv)]
+
+    def _drop_cache(self):
+        self._ops = {}
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        for name, m in self._leaves():
+            if name + ".weight_v" in state_dict:
+                m.set_form(True)
+            elif name + ".weight" in state_dict:
+                m.set_form(False)
+        self._drop_cache()
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
+    def _apply(self, fn, *a, **kw):
+        self._drop_cache()
+        return super()._apply(fn, *a, **kw)
+
+    def remove_weight_norm(self):
+        """Replace (weight_g, weight_v) by the folded weight -- the fp32 values the kernels' operands were laid out from, so no
+        output changes."""
+        for name, m in self._leaves():
+            if not m.normed:
+                continue
+            if m.weight_v.is_cuda:
+                w = self._fold(name, m, None, want_op=False)[0]
+            else:
+                v = m.weight_v.detach()
+                w = v * (m.weight_g.detach() / v.flatten(1).norm(dim=1).view(-1, 1, 1))
+            m.set_form(False, w.to(m.bias.dtype))
+        self._drop_cache()
+
+    # ---- operands ---------------------------------------------------------------------------------------------------------
+    def _layer_mode(self, name):
+        if name.startswith("ups."):
+            return 1, self.upsample_factors[int(name.split(".")[1])]
+        return (2, 1) if name == "conv_post" else (0, 1)
+
+    def _fold(self, name, m, dtype, want_w32=True, want_op=True):
+        mode, u = self._layer_mode(name)
+        with torch.no_grad():
+            if m.normed:
+                v, g = m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
+            else:
+                v, g = m.weight.detach().float().contiguous(), None
+            return KV.hifigan_fold(mode, v, g, torch.float32 if dtype is None else dtype, u=u, want_w32=want_w32, want_op=want_op)
+
+    def _operands(self, dtype):
+        """Folded weights in the kernels' layouts for `dtype`: built once per load / device move, on the device."""
+        if dtype not in self._ops:
+            ops = {}
+            for name, m in self._leaves():
+                _, op = self._fold(name, m, dtype, want_w32=False)
+                ops[name] = (op, m.bias.detach().float().contiguous())
+            self._ops[dtype] = ops
+        return self._ops[dtype]
+
+    # ---- the launch list --------------------------------------------------------------------------------------------------
+    def launch_plan(self):
+        """What one call launches, in order: dicts with `kind` in KINDS, the layer, source / destination buffers and the fused
+        prologue / epilogue options.  forward() executes exactly this list."""
+        uc = self.upsample_channels
+        plan = [dict(kind="input", dst="x", cout=self.in_channels, mul=1),
+                dict(kind="conv1d", layer="conv_pre", src="x", dst="pre", k=5, dil=1, cin=self.in_channels, cout=uc, slope=0.0, mul=1,
+                     tap="conv_pre")]
+        cur, mul = "pre", 1
+        for i, (u, k) in enumerate(zip(self.upsample_factors, self.upsample_kernel_sizes)):
+            cin, ch = uc // 2 ** i, uc // 2 ** (i + 1)
+            plan.append(dict(kind="tconv1d", layer=f"ups.{i}", src=cur, dst=f"up{i}", k=k, u=u, cin=cin, cout=ch, slope=LRELU_SLOPE,
+                             mul=mul, tap=f"ups.{i}"))
+            mul *= u
+            for j, (rk, dils) in enumerate(zip(self.resblock_kernel_sizes, self.resblock_dilation_sizes)):
+                x = f"up{i}"
+                rb = f"resblocks.{i * self.num_kernels + j}"
+                for q, d in enumerate(dils):
+                    last = q == len(dils) - 1
+                    plan.append(dict(kind="conv1d", layer=f"{rb}.convs1.{q}", src=x, dst=f"t{i}", k=rk, dil=d, cin=ch, cout=ch,
+                                     slope=LRELU_SLOPE, mul=mul))
+                    e = dict(kind="conv1d", layer=f"{rb}.convs2.{q}", src=f"t{i}", res=x, k=rk, dil=1, cin=ch, cout=ch, slope=LRELU_SLOPE,
+                             mul=mul)
+                    if last:      # x = xt + x is the block's output: it goes straight into the MRF average of the stage
+                        e.update(dst=f"s{i}", accumulate=j > 0, scale=1.0 / self.num_kernels)
+                        if j == self.num_kernels - 1:
+                            e["tap"] = f"stage.{i}"
+                    else:
+                        x = f"a{i}" if x != f"a{i}" else f"b{i}"
+                        e.update(dst=x)
+                    plan.append(e)
+            cur = f"s{i}"
+        plan.append(dict(kind="conv_out", layer="conv_post", src=cur, k=7, cin=ch, slope=POST_SLOPE, mul=mul))
+        return plan
+
+    # ---- execution --------------------------------------------------------------------------------------------------------
+    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None):
+        if not x.is_cuda:
+            raise RuntimeError("HifiganGenerator needs GPU tensors (there is no CPU path)")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError("HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError("HifiganGenerator input: float32 or bfloat16")
+        dtype = Fn.compute_dtype()
+        ops = self._operands(dtype)
+        bufs, y = {}, None
+        with torch.no_grad():
+            for e in self.launch_plan():
+                kind = e["kind"]
+                if kind == "input":
+                    bufs[e["dst"]] = KV.hifigan_input(x.detach(), B, N, e["cout"], strides, dtype, a=a, b=b, vlens=vlens)
+                    continue
+                w, bias = ops[e["layer"]]
+                src = bufs[e["src"]]
+                if kind == "conv_out":
+                    y, pre = KV.hifigan_conv_out(src, w, bias, e["k"], slope=e["slope"], tanh=True, want_pre=taps is not None, vlens=vlens,
+                                                 vmul=e["mul"])
+                    if taps is not None:
+                        taps["conv_post"] = pre
+                elif kind == "tconv1d":
+                    bufs[e["dst"]] = KV.hifigan_tconv1d(src, w, bias, e["k"], e["u"], e["cout"], slope=e["slope"], out=bufs.get(e["dst"]),
+                                                        vlens=vlens, vmul=e["mul"])
+                else:
+                    res = bufs[e["res"]] if "res" in e else None
+                    bufs[e["dst"]] = KV.hifigan_conv1d(src, w, bias, e["k"], e["dil"], e["cout"], slope=e["slope"], res=res,
+                                                       accumulate=e.get("accumulate", False), scale=e.get("scale", 1.0),
+                                                       out=bufs.get(e["dst"]), vlens=vlens, vmul=e["mul"])
+                if taps is not None and "tap" in e:
+                    taps[e["tap"]] = bufs[e["dst"]]
+        return y
+
+    def forward(self, x, taps=None):
+        """x (B, in_channels, N) -> (B, 1, N * prod(upsample_factors)) fp32.  taps: a dict that receives the channel-last outputs of
+        conv_pre, every ups[i], every stage (after the MRF average) and conv_post before tanh (tests)."""
+        if x.dim() != 3 or x.shape[1] != self.in_channels:
+            raise ValueError(f"HifiganGenerator: x (B, {self.in_channels}, N) expected, got {tuple(x.shape)}")
+        B, _, N = x.shape
+        y = self._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps)
+        return y.view(B, 1, -1)
+
+    def forward_batch(self, xs, lens, a=None, b=None, host_lens=None):
+        """xs (B, Nmax, in_channels) channel-last, zero-padded (whatever the padding holds is never read); lens (B) mel frames ->
+        list of B waveforms of lens[b] * prod(upsample_factors) samples, each what the utterance gets alone.
+        lens: a list / CPU tensor, or an int32 device tensor (what the kernels read).  Only the slicing of the result needs the
+        lengths on the host: pass them as host_lens beside a device tensor and the call never waits for the device; without
+        host_lens a device tensor is read back AFTER every launch has been queued."""
+        if xs.dim() != 3 or xs.shape[2] != self.in_channels:
+            raise ValueError(f"HifiganGenerator: xs (B, Nmax, {self.in_channels}) expected, got {tuple(xs.shape)}")
+        B, N, _ = xs.shape
+        on_device = isinstance(lens, torch.Tensor) and lens.is_cuda
+        if on_device and (lens.dtype != torch.int32 or not lens.is_contiguous() or lens.numel() != B):
+            raise ValueError("forward_batch: device lengths are a contiguous int32 tensor with one value per row")
+        host = host_lens if on_device else lens
+        if host is not None:
+            host = [int(n) for n in (host.tolist() if isinstance(host, torch.Tensor) else host)]
+            if len(host) != B or any(n < 0 or n > N for n in host):
+                raise ValueError("forward_batch: one length per row, 0 <= lens[b] <= Nmax")
+        vlens = lens if on_device else torch.tensor(host, dtype=torch.int32).to(xs.device)
+        y = self._run(xs, B, N, (xs.stride(0), xs.stride(1), xs.stride(2)), vlens=vlens, a=a, b=b)
+        if host is None:
+            host = [min(max(int(n), 0), N) for n in lens.tolist()]
+        total = stage_lengths(host, self.upsample_factors)[-1]
+        return [y[i, :total[i]] for i in range(B)]
+
+
+class HifiganVocoder:
+    """The call shape of the reference's Vocoder (vocoder/vocoder.py:10-61) over a HifiganGenerator whose in_channels = n_mels:
+    decode(c) de-normalises c (T, n_mels) with the target statistics, normalises with the vocoder's and generates.  The two
+    affine maps are one per-bin a * c + b applied by the input launch.  stats / trg_stats: dicts of arrays `mean`, `scale`."""
+
+    def __init__(self, generator, stats, trg_stats=None, take_norm_feat=True):
+        if take_norm_feat and trg_stats is None:
+            raise ValueError("trg_stats must be given if take_norm_feat=True")
+        self.generator, self.take_norm_feat = generator, take_norm_feat
+        mean, scale = np.asarray(stats["mean"], np.float64), np.asarray(stats["scale"], np.float64)
+        if take_norm_feat:
+            tm, ts = np.asarray(trg_stats["mean"], np.float64), np.asarray(trg_stats["scale"], np.float64)
+            a, b = ts / scale, (tm - mean) / scale
+        else:
+            a, b = 1.0 / scale, -mean / scale
+        if a.shape != (generator.in_channels,):
+            raise ValueError("statistics must have one value per input channel of the generator")
+        self._a, self._b = torch.from_numpy(a).float(), torch.from_numpy(b).float()
+
+    def _affine(self, device):
+        if self._a.device != device:
+            self._a, self._b = self._a.to(device), self._b.to(device)
+        return self._a, self._b
+
+    def decode(self, c):
+        y, sr = self.decode_batch(c.unsqueeze(0), [c.shape[0]])
+        return y[0], sr
+
+    def decode_batch(self, cs, lens, host_lens=None):
+        a, b = self._affine(cs.device)
+        return self.generator.forward_batch(cs, lens, a=a, b=b, host_lens=host_lens), self.generator.sample_rate
