@@ -731,6 +731,36 @@ int s2svc_hifigan_input(int in_dtype, int out_dtype, int B, int T, int C, const 
 int s2svc_hifigan_fold(int mode, int D0, int D1, int k, int u, const float* g, const float* v, float* w32, int op_dtype, void* w_op,
                        void* stream);
 
+/* ========================================================================================== */
+/* Griffin-Lim phase reconstruction, fp32 (csrc/griffin_lim.hip): librosa.griffinlim with      */
+/* init="random" as vocoder/griffin_lim.py:53-106 calls it, for a batch with per-row lengths   */
+/* in 2 n_iter + 3 launches.  Buffers: S (B, Tmax, bins) fp32, X / Rprev (B, Tmax, bins)       */
+/* complex (re, im interleaved), frames (B, Tmax, n_fft) fp32, bins = n_fft / 2 + 1.  Absent   */
+/* rows: frames t >= lens[b] (lens = NULL: every frame present) enter no sum and are never     */
+/* read; prepare writes their S / X / Rprev as zero.  A row with fewer than two frames has no  */
+/* samples and is absent as a whole.  `tables` (8-byte aligned fp32): exp(-2 pi i m / (N/2))   */
+/* [N/2] complex | exp(-2 pi i k / N) [N/2 + 1] complex | window zero-padded to N [N].         */
+/* ========================================================================================== */
+/* n_fft the kernels transform: 512, 1024, 2048 */
+int s2svc_gl_supported(int n_fft);
+/* x (B, Tmax, D) -> S and X = S exp(2 pi i u).  pinv_t (nmel, bins) given: D = nmel, S = max(eps, pinv . 10^(x * scale + mean))
+   (vocoder/griffin_lim.py:20-50; scale / mean [D] or both NULL); pinv_t = NULL: D = bins, S = |x * scale + mean|.
+   u (B, Tmax, bins) in [0, 1) or NULL: drawn from a counter-based generator over (seed, row, frame, bin).
+   X, Rprev, nsamp ([B] int32: hop * (frames - 1)) may be NULL. */
+int s2svc_gl_prepare(int B, int Tmax, int nb, int D, int nmel, int hop, const float* x, const float* scale, const float* mean,
+                     const float* pinv_t, float eps, const float* u, uint64_t seed, const int32_t* lens, float* S, float* X,
+                     float* Rprev, int32_t* nsamp, void* stream);
+/* frames[b, t] = window * irfft(X[b, t]) (the imaginary parts of bins 0 and N/2 are ignored, as numpy's irfft does) */
+int s2svc_gl_synth(int B, int Tmax, int n_fft, const float* X, const int32_t* lens, const float* tables, float* frames, void* stream);
+/* One iteration's second half.  R[b, t] = frame t of stft(y, center=True, zero (reflect = 0) or reflect padding), y = the overlap-add of
+   `frames` over the squared-window envelope (where it exceeds FLT_MIN), trimmed by N/2: every sample is gathered from the frames that
+   cover it in ascending frame order.  A = R - coef * Rprev (have_prev) or R;  X = S A / (|A| + FLT_MIN);  Rprev = R.  In place. */
+int s2svc_gl_analyse(int B, int Tmax, int n_fft, int hop, int reflect, const float* frames, const float* S, const int32_t* lens,
+                     const float* tables, float coef, int have_prev, float* X, float* Rprev, void* stream);
+/* y (B, hop * (Tmax - 1)): the same gather, one lane per sample; zero past a row's hop * (lens[b] - 1) samples */
+int s2svc_gl_ola(int B, int Tmax, int n_fft, int hop, const float* frames, const int32_t* lens, const float* tables, float* y,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
