@@ -222,11 +222,6 @@ class OverlappedBackward:
         """Backward of stage i: from a loss (`loss:<key>`) or from below a cut (`cut:<name>`) -- or from several such roots, in
         the order given -- then the join of the parameter-gradient side work, so that the stage's slices of the flat gradient
         buffer are final on the current stream."""
-        if i == 0 and hasattr(self.opt, "join_prologue"):
-            self.opt.join_prologue()                             # zero-filled gradients + refreshed weight copies (FlatAdam.begin_step)
-        return self._run_stage(i, losses, scale)
-
-    def _run_stage(self, i, losses, scale=None):
         roots = self.plan[i]["root"]
         branch_root = self.plan[i].get("branch_root")           # a loss (or a cut) whose sub-network ran on the auxiliary stream
         fork = None

@@ -53,11 +53,10 @@ def _wcast(w, dtype):
 def _dgrad_operand(weight, w, n_out, n_in, dtype):
     """The weight as B operand of dX[M, n_in] = dY[M, n_out] . W[n_out, n_in]  (B(row = k', red = n') = W[n', k']).
     With the optimiser's transposed bf16 shadow (FlatAdam, `_s2s_bf16_t` = W^T (n_in, n_out)) that operand is
-    K-contiguous and the GEMM runs on the all-DMA kernel; otherwise W is read row-contiguous (register transposes)."""
+    K-contiguous and the GEMM runs on the all-DMA kernel; otherwise W is read row-contiguous (register transposes).
+    The transposed shadow is always current: FlatAdam.step() and refresh_shadow() rewrite it in line (refresh_derived)."""
     wt = getattr(weight, "_s2s_bf16_t", None) if dtype == torch.bfloat16 else None
     if wt is not None:
-        weight._s2s_perm_registry.sync()       # the transposed shadow is refreshed by the step prologue (optim.FlatAdam.begin_step);
-        #                                        every tensor that carries `_s2s_bf16_t` carries the registry (optim.FlatAdam)
         return K.operand(wt, n_out)
     return K.operand(w, n_in, layout=K.RC)
 

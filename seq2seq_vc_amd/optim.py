@@ -12,11 +12,126 @@ device tensor, so the optimiser step is hipGraph-capturable and needs no host sy
 flat gradient buffer is also what data-parallel training all-reduces (distributed.py): a handful of
 large RCCL collectives instead of one per tensor.
 """
-import os
+import collections
 
 import torch
 
 from .ops import kernels as K
+
+
+# What plan_layout returns.  params / offsets: the trainable parameters in flat order and where each starts; numel: the flat element
+# count; groups / stacks: the Q|K|V groups and decoder K|V stacks that turned out contiguous (dicts of _attention_groups /
+# _source_attention_stacks plus "ow", "ob": offsets of their first weight and bias); t_table: the transposed-shadow table, one
+# (source offset, destination offset, rows, cols, owner) per matrix, owner = the parameter, or (object, attribute, key) of a
+# fused view that FlatAdam attaches (module._fused["w_qkv"], decoder._src_kv_all["w"]); t_numel: elements of the transposed buffer.
+Layout = collections.namedtuple("Layout", "params offsets numel groups stacks t_table t_numel")
+
+
+def _round_up(n, align):
+    return (n + align - 1) // align * align
+
+
+def _source_attention_stacks(model):
+    """Per modules.Decoder: the K / V weights and biases of the source-attention blocks of all its layers, in layer order
+    (k_1, v_1, k_2, v_2, ...)."""
+    from .modules import Decoder, MultiHeadedAttention
+    stacks = []
+    for dec in model.modules():
+        if not isinstance(dec, Decoder):
+            continue
+        mods = [layer.src_attn for layer in dec.decoders]
+        if not mods or not all(type(m) is MultiHeadedAttention for m in mods):
+            continue
+        ws = [w for m in mods for w in (m.linear_k.weight, m.linear_v.weight)]
+        bs = [b for m in mods for b in (m.linear_k.bias, m.linear_v.bias)]
+        qs = [p for m in mods for p in (m.linear_q.weight, m.linear_q.bias)]
+        if all(p is not None and p.requires_grad for p in ws + bs + qs) and len({w.shape for w in ws}) == 1:
+            stacks.append({"decoder": dec, "mods": mods, "w": ws, "b": bs})
+    return stacks
+
+
+def _attention_groups(model, skip=()):
+    from .modules import MultiHeadedAttention
+    groups = []
+    for m in model.modules():
+        if id(m) in skip:
+            continue
+        if isinstance(m, MultiHeadedAttention):
+            ws = [m.linear_q.weight, m.linear_k.weight, m.linear_v.weight]
+            bs = [m.linear_q.bias, m.linear_k.bias, m.linear_v.bias]
+            if all(p is not None and p.requires_grad for p in ws + bs):
+                groups.append({"module": m, "w": ws, "b": bs})
+    return groups
+
+
+def _flat_order(params, runs):
+    """The parameters in flat order: every run (group or stack) moves, weights then biases, to where its first weight stood.
+    Also the ids of the `tight` members, which start right where their predecessor ends (no alignment gap)."""
+    first = {id(r["w"][0]): r for r in runs}
+    in_run = {id(p) for r in runs for p in r["w"] + r["b"]}
+    ordered, tight = [], set()
+    for p in params:
+        if id(p) in first:
+            r = first[id(p)]
+            ordered += r["w"] + r["b"]
+            if all(q.numel() % 8 == 0 for q in r["w"] + r["b"]):
+                tight.update(id(q) for q in r["w"][1:] + r["b"][1:])
+        elif id(p) not in in_run:
+            ordered.append(p)
+    return ordered, tight
+
+
+def _contiguous(run, off_of):
+    """Do the weights of a run lie back to back as ONE (len * D, D) matrix, and its biases as one vector?  Records "ow" / "ob"."""
+    D = run["w"][0].shape[0]
+    run["ow"], run["ob"] = ow, ob = off_of[id(run["w"][0])], off_of[id(run["b"][0])]
+    return all(off_of[id(w)] == ow + i * D * D for i, w in enumerate(run["w"])) and \
+        all(off_of[id(b)] == ob + i * D for i, b in enumerate(run["b"]))
+
+
+def _transposed_table(params, offsets, numel, groups, stacks, align):
+    """Matrices (Linear, 1x1 Conv1d) keep their offset in the transposed buffer; the fused views get extra room behind `numel`."""
+    table = [(o, o, p.shape[0], p.shape[1], p) for p, o in zip(params, offsets)
+             if p.dim() == 2 or (p.dim() == 3 and p.shape[-1] == 1)]
+    extras = []
+    for g in groups:
+        D = g["w"][0].shape[0]
+        extras += [(g["ow"], 3 * D, D, (g["module"], "_fused", "w_qkv")), (g["ow"] + D * D, 2 * D, D, (g["module"], "_fused", "w_kv"))]
+    for st in stacks:
+        D = st["w"][0].shape[0]
+        extras.append((st["ow"], len(st["w"]) * D, D, (st["decoder"], "_src_kv_all", "w")))
+    end = numel
+    for off, rows, cols, owner in extras:
+        table.append((off, end, rows, cols, owner))
+        end += _round_up(rows * cols, align)
+    return table, end
+
+
+def plan_layout(model, align=64, fuse_qkv=True, transposed=True):
+    """The flat layout of the trainable parameters of `model` (a Layout): pure host arithmetic, allocates nothing, works on a CPU
+    model.  Offsets are multiples of `align` except inside a run.  The Q / K / V weights (and biases) of every attention module lie
+    back to back, so that [Wq;Wk;Wv] is ONE (3D, D) matrix (fused projection GEMMs, modules.py); so do the source-attention K / V
+    weights of all layers of a decoder, [Wk_1; Wv_1; ...; Wk_L; Wv_L] (the memory is projected for all layers by a single GEMM,
+    modules.Decoder.forward).  Packed projections, the flat gradient slots, the data-parallel buckets (param_ranges) and the flat
+    checkpoint format all hang on these offsets."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params:
+        raise ValueError("no trainable parameters")
+    stacks = _source_attention_stacks(model) if fuse_qkv else []
+    groups = _attention_groups(model, skip={id(m) for st in stacks for m in st["mods"]}) if fuse_qkv else []
+    ordered, tight = _flat_order(params, groups + stacks)
+    offsets, n = [], 0
+    for p in ordered:
+        if id(p) not in tight:
+            n = _round_up(n, align)
+        offsets.append(n)
+        n += p.numel()
+    n = _round_up(n, align)
+    off_of = {id(p): o for p, o in zip(ordered, offsets)}
+    groups = [g for g in groups if _contiguous(g, off_of)]
+    stacks = [st for st in stacks if _contiguous(st, off_of)]
+    table, t_numel = _transposed_table(ordered, offsets, n, groups, stacks, align) if transposed else ([], n)
+    return Layout(ordered, offsets, n, groups, stacks, table, t_numel)
 
 
 class FlatAdam:
@@ -25,41 +140,15 @@ class FlatAdam:
         # torch.optim.Adam(model.parameters()) -- what the reference builds (bin/vc_train.py:405-416) -- numbers its state by
         # position in model.parameters(), frozen parameters included; kept for checkpoint interchange (state_dict below)
         self.all_params = list(model.parameters())
-        self.params = [p for p in self.all_params if p.requires_grad]
-        if not self.params:
-            raise ValueError("no trainable parameters")
         self._model = model
-        # lay the Q/K/V weights (and biases) of every attention module out back to back, so that
-        # [Wq;Wk;Wv] is ONE (3D, D) matrix in the flat buffer (fused projection GEMMs, see modules.py)
-        stacks = self._source_attention_stacks(model) if fuse_qkv else []
-        in_stack = {id(m) for st in stacks for m in st["mods"]}
-        groups = self._attention_groups(model, skip=in_stack) if fuse_qkv else []
-        grouped = {id(p) for g in groups for p in g["w"] + g["b"]} | {id(p) for st in stacks for p in st["w"] + st["b"]}
-        first = {id(g["w"][0]): g for g in groups}
-        first.update({id(st["w"][0]): st for st in stacks})
-        ordered, tight = [], set()     # `tight` members start right where the previous one ends (no alignment gap)
-        for p in self.params:
-            if id(p) in first:
-                g = first[id(p)]
-                ordered += g["w"] + g["b"]
-                if all(q.numel() % 8 == 0 for q in g["w"] + g["b"]):
-                    tight.update(id(q) for q in g["w"][1:] + g["b"][1:])
-            elif id(p) not in grouped:
-                ordered.append(p)
-        self.params = ordered
+        plan = plan_layout(model, align, fuse_qkv, transposed=bf16_shadow and transposed_shadow)
+        self.params, self.offsets, self.numel = plan.params, plan.offsets, plan.numel
         dev = self.params[0].device
         if dev.type != "cuda":
             raise RuntimeError("FlatAdam needs the model on the GPU (there is no CPU path)")
         self.lr, self.betas, self.eps = float(lr), betas, float(eps)
         self.grad_norm, self.warmup_steps = float(grad_norm), float(warmup_steps or 0)
-        offs, n = [], 0
-        for p in self.params:
-            if id(p) not in tight:
-                n = (n + align - 1) // align * align
-            offs.append(n)
-            n += p.numel()
-        n = (n + align - 1) // align * align
-        self.offsets, self.numel = offs, n
+        n = self.numel
         self.flat_p = torch.zeros(n, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -68,10 +157,17 @@ class FlatAdam:
         self.state = torch.zeros(4, dtype=torch.float32, device=dev)  # step, lr, grad_norm, clip_coef
         self.partial = torch.empty(1024, dtype=torch.float64, device=dev)
         self._perm_jobs = K.PermRegistry()   # (parameter, permutation, persistent buffer): filled by ops.kernels.gather3_cached
-        self._perm_jobs.refresh = self._refresh_transposed
-        self._zero_due = False
-        self._began = False           # begin_step() was called since the last step()
-        for p, o in zip(self.params, offs):
+        self._adopt_parameters()
+        self._attach_fused_views(plan)
+        self.shadow_t = self.t_tiles = None
+        if plan.t_table:
+            self._attach_transposed(plan)
+        if self.shadow is not None:
+            self.refresh_shadow()
+
+    def _adopt_parameters(self):
+        """Move the parameters into flat_p and point their gradient (and bf16 shadow) at the parallel buffers."""
+        for p, o in zip(self.params, self.offsets):
             k = p.numel()
             self.flat_p[o:o + k].copy_(p.data.reshape(-1))
             p.data = self.flat_p[o:o + k].view(p.shape)
@@ -80,96 +176,36 @@ class FlatAdam:
             p._s2s_perm_registry, p._s2s_perms = self._perm_jobs, {}
             if self.shadow is not None:
                 p._s2s_bf16 = self.shadow[o:o + k].view(p.shape)
-        off_of = {id(p): o for p, o in zip(self.params, offs)}
-        # transposed bf16 shadow of the matrix-shaped weights (Linear, 1x1 Conv1d): dX = dY.W then reads a K-contiguous
-        # operand and runs on the all-DMA GEMM kernel.  Matrices keep their offset; fused QKV / KV views get extra room.
-        self.shadow_t, self._t_descs, self._t_extra = None, [], n
-        if self.shadow is not None and transposed_shadow:
-            for p, o in zip(self.params, offs):
-                if p.dim() == 2 or (p.dim() == 3 and p.shape[-1] == 1):
-                    self._t_descs.append((o, o, p.shape[0], p.shape[1], p))
-        for g in groups:
-            ws, bs = g["w"], g["b"]
-            D = ws[0].shape[0]
-            ow, ob = off_of[id(ws[0])], off_of[id(bs[0])]
-            contiguous = all(off_of[id(ws[i])] == ow + i * D * D for i in range(3)) and \
-                all(off_of[id(bs[i])] == ob + i * D for i in range(3))
-            if contiguous:
-                g["module"]._fused = {
-                    "w_qkv": self._view(ow, (3 * D, D)), "b_qkv": self._view(ob, (3 * D,)),
-                    "w_q": self._view(ow, (D, D)), "b_q": self._view(ob, (D,)),
-                    "w_kv": self._view(ow + D * D, (2 * D, D)), "b_kv": self._view(ob + D, (2 * D,))}
-                if self.shadow is not None and transposed_shadow:
-                    f = g["module"]._fused
-                    for key, off, rows in (("w_qkv", ow, 3 * D), ("w_kv", ow + D * D, 2 * D)):
-                        self._t_descs.append((off, self._t_extra, rows, D, f[key]))
-                        self._t_extra += (rows * D + align - 1) // align * align
-        # decoder stacks: [Wk_1; Wv_1; ...; Wk_L; Wv_L] of the source-attention blocks is ONE (L*2D, D) matrix -- the memory is
-        # projected for all layers by a single GEMM (modules.Decoder.forward); each block keeps its own (2D, D) view
-        for st in stacks:
-            ws, bs, mods = st["w"], st["b"], st["mods"]
-            D = ws[0].shape[0]
-            ow, ob = off_of[id(ws[0])], off_of[id(bs[0])]
-            contiguous = all(off_of[id(w)] == ow + i * D * D for i, w in enumerate(ws)) and \
-                all(off_of[id(b)] == ob + i * D for i, b in enumerate(bs))
-            if not contiguous:
-                continue
-            for li, m in enumerate(mods):
-                q_w, q_b = m.linear_q.weight, m.linear_q.bias
-                m._fused = {"w_q": q_w, "b_q": q_b,
+
+    def _attach_fused_views(self, plan):
+        """module._fused of every contiguous Q|K|V group and source-attention block, decoder._src_kv_all of every stack."""
+        for g in plan.groups:
+            D, ow, ob = g["w"][0].shape[0], g["ow"], g["ob"]
+            g["module"]._fused = {
+                "w_qkv": self._view(ow, (3 * D, D)), "b_qkv": self._view(ob, (3 * D,)),
+                "w_q": self._view(ow, (D, D)), "b_q": self._view(ob, (D,)),
+                "w_kv": self._view(ow + D * D, (2 * D, D)), "b_kv": self._view(ob + D, (2 * D,))}
+        for st in plan.stacks:                  # each block keeps its own (2D, D) view of the stack
+            D, ow, ob = st["w"][0].shape[0], st["ow"], st["ob"]
+            for li, m in enumerate(st["mods"]):
+                m._fused = {"w_q": m.linear_q.weight, "b_q": m.linear_q.bias,
                             "w_kv": self._view(ow + li * 2 * D * D, (2 * D, D)), "b_kv": self._view(ob + li * 2 * D, (2 * D,))}
-            allv = {"w": self._view(ow, (len(ws) * D, D)), "b": self._view(ob, (len(bs) * D,))}
-            st["decoder"]._src_kv_all = allv
-            if self.shadow is not None and transposed_shadow:
-                self._t_descs.append((ow, self._t_extra, len(ws) * D, D, allv["w"]))
-                self._t_extra += (len(ws) * D * D + align - 1) // align * align
-        if self._t_descs:
-            self.shadow_t = torch.zeros(self._t_extra, dtype=torch.bfloat16, device=dev)
-            tiles = []
-            for so, do, rows, cols, t in self._t_descs:
-                t._s2s_bf16_t = self.shadow_t[do:do + rows * cols].view(cols, rows)
-                nt = ((rows + 63) // 64) * ((cols + 63) // 64)
-                tiles += [(so, do, (rows << 32) | cols, i) for i in range(nt)]
-            self.t_tiles = torch.tensor(tiles, dtype=torch.int64, device=dev)
-            for g in groups:                                                   # w_q view: the transposed copy of linear_q.weight
-                f = getattr(g["module"], "_fused", None)
-                if f is not None:
-                    f["w_q"]._s2s_bf16_t = g["w"][0]._s2s_bf16_t
-        if self.shadow is not None:
-            self.refresh_shadow()
+            st["decoder"]._src_kv_all = {"w": self._view(ow, (len(st["w"]) * D, D)), "b": self._view(ob, (len(st["b"]) * D,))}
 
-    @staticmethod
-    def _source_attention_stacks(model):
-        """Per modules.Decoder: the K / V weights and biases of the source-attention blocks of all its layers, in layer order
-        (k_1, v_1, k_2, v_2, ...)."""
-        from .modules import Decoder, MultiHeadedAttention
-        stacks = []
-        for dec in model.modules():
-            if not isinstance(dec, Decoder):
-                continue
-            mods = [layer.src_attn for layer in dec.decoders]
-            if not mods or not all(type(m) is MultiHeadedAttention for m in mods):
-                continue
-            ws = [w for m in mods for w in (m.linear_k.weight, m.linear_v.weight)]
-            bs = [b for m in mods for b in (m.linear_k.bias, m.linear_v.bias)]
-            qs = [p for m in mods for p in (m.linear_q.weight, m.linear_q.bias)]
-            if all(p is not None and p.requires_grad for p in ws + bs + qs) and len({w.shape for w in ws}) == 1:
-                stacks.append({"decoder": dec, "mods": mods, "w": ws, "b": bs})
-        return stacks
-
-    @staticmethod
-    def _attention_groups(model, skip=()):
-        from .modules import MultiHeadedAttention
-        groups = []
-        for m in model.modules():
-            if id(m) in skip:
-                continue
-            if isinstance(m, MultiHeadedAttention):
-                ws = [m.linear_q.weight, m.linear_k.weight, m.linear_v.weight]
-                bs = [m.linear_q.bias, m.linear_k.bias, m.linear_v.bias]
-                if all(p is not None and p.requires_grad for p in ws + bs):
-                    groups.append({"module": m, "w": ws, "b": bs})
-        return groups
+    def _attach_transposed(self, plan):
+        """The transposed bf16 shadow of the matrix-shaped weights: dX = dY.W then reads a K-contiguous operand and runs on the
+        all-DMA GEMM kernel.  `_s2s_bf16_t` on every owner of plan.t_table, and the tile list of the batched transpose."""
+        dev = self.flat_p.device
+        self.shadow_t = torch.zeros(plan.t_numel, dtype=torch.bfloat16, device=dev)
+        tiles = []
+        for so, do, rows, cols, owner in plan.t_table:
+            t = owner if isinstance(owner, torch.Tensor) else getattr(owner[0], owner[1])[owner[2]]
+            t._s2s_bf16_t = self.shadow_t[do:do + rows * cols].view(cols, rows)
+            nt = ((rows + 63) // 64) * ((cols + 63) // 64)
+            tiles += [(so, do, (rows << 32) | cols, i) for i in range(nt)]
+        self.t_tiles = torch.tensor(tiles, dtype=torch.int64, device=dev)
+        for g in plan.groups:                   # w_q view: the transposed copy of linear_q.weight
+            g["module"]._fused["w_q"]._s2s_bf16_t = g["w"][0]._s2s_bf16_t
 
     def _view(self, off, shape):
         """A trainable-looking view of the flat buffers (fp32 master, flat-gradient slot, bf16 shadow)."""
@@ -194,14 +230,14 @@ class FlatAdam:
         self._touch()
         if self.shadow is not None:
             self.shadow.copy_(K.cast(self.flat_p, torch.bfloat16))
-        self._refresh_transposed()
+        self.refresh_derived()
 
-    def _refresh_transposed(self):
-        """Derived copies of the weights: the transposed bf16 shadow and the permuted convolution weights that the forward /
-        backward passes registered (ops.kernels.gather3_cached) -- one launch each.  The permuted copies first: the forward pass
-        needs them (PermRegistry.ev_perm), the transposed shadow only feeds data-gradient GEMMs."""
+    def refresh_derived(self):
+        """Every derived copy of the weights, in line on the current stream -- called from exactly step() and refresh_shadow(), so
+        nothing that reads a copy can see a stale one: the permuted convolution weights that the forward / backward passes
+        registered (ops.kernels.gather3_cached; one grouped launch), then the transposed bf16 shadow (one tile-transpose launch).
+        Copies that a captured refresh cannot know (`covered`) are gathered again on use."""
         reg = self._perm_jobs
-        reg.due = False
         K.gather3_refresh(reg)
         if self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing():
             # a captured refresh updates exactly the copies registered NOW on every replay; copies that register later (first
@@ -210,46 +246,28 @@ class FlatAdam:
         if self.shadow_t is not None:
             K.transpose_tiles(self.t_tiles, self.shadow, self.shadow_t)
 
-    # -- the step prologue -------------------------------------------------------------------------------------------------
     # After an optimiser step three memory-bound passes stand between it and the next backward pass: the permuted convolution
     # weights (needed by the forward pass), the transposed bf16 shadow (data-gradient GEMMs) and the zero-fill of the flat
     # gradient buffer (weight-gradient kernels accumulate): 136 + 144 + 80 us of a 13 ms AAS-VC step, 32 + 27 + 18 us of a
     # 4.0 ms VTN step.  They run IN LINE: the refresh at the end of step(), the zero-fill in begin_step() / zero_grad().
-    # (Rounds 3-5 carried an opt-in that ran them on a prologue stream beside the forward pass: 13.0 vs 12.74 ms per AAS-VC step,
-    # VTN equal; as capped grids of 16 ... 2048 workgroups 11.52-11.59 vs 11.40 ms -- what runs beside the forward chain is not
-    # free even when it is HBM-bound.  Removed in round 6; profiles/AB_LOG.md.)
+    # (Running them on a stream of their own beside the forward pass lost: 13.0 vs 12.74 ms per AAS-VC step, VTN equal; as capped
+    # grids of 16 ... 2048 workgroups 11.52-11.59 vs 11.40 ms -- what runs beside the forward chain is not free even when it is
+    # HBM-bound.  profiles/AB_LOG.md.)
 
     def begin_step(self, zero=True):
-        """First call of a training step (before the forward pass).  zero: True = clear the gradients, None = only if a
-        zero_grad(defer=True) is pending (gradient accumulation), False = leave them."""
-        reg = self._perm_jobs
-        if zero is None:
-            zero = self._zero_due
-        self._zero_due = False
-        self._began = True
-        if reg.due:
-            self._refresh_transposed()
+        """First call of a training step (before the forward pass): clear the gradients unless the caller keeps them (gradient
+        accumulation, or a trainer that clears them after its optimiser step)."""
         if zero:
             self._zero_gradients()
 
     def join_prologue(self):
-        """The current stream (the one that starts the backward pass) waits for the prologue."""
-        if self._zero_due:                       # zero_grad(defer=True) without a begin_step() since
-            self._zero_due = False
-            self._zero_gradients()
-        self._perm_jobs.join()
+        """Empty on purpose: bench.py calls it before the backward pass and is not ours to change; there is nothing to join."""
 
     def _zero_gradients(self):
         if self.flat_g.is_cuda:
             K.zero_(self.flat_g)                 # (a launch of this library: no ATen kernel inside a captured step)
         else:
             self.flat_g.zero_()
-
-    def param_range(self, module):
-        """[lo, hi) of the flat buffers covered by the parameters of `module`, or None if parameters of other modules
-        lie inside that range."""
-        r = self.param_ranges([module])
-        return r[0] if r is not None and len(r) == 1 else None
 
     def param_ranges(self, modules):
         """Maximal contiguous [lo, hi) ranges of the flat buffers that hold exactly the trainable parameters of `modules`
@@ -272,18 +290,14 @@ class FlatAdam:
                 cur = None
         return [tuple(r) for r in ranges]
 
-    def zero_grad(self, set_to_none=False, defer=False):
-        """The zero-fill of the flat gradient buffer, in line.  `defer` is accepted from the trainers that clear the gradients AFTER
-        the optimiser step (it used to move the fill into the next begin_step(); the fill is one launch either way)."""
-        self._zero_due = False
+    def zero_grad(self, set_to_none=False):
+        """The zero-fill of the flat gradient buffer, in line (the gradients are views of it: never set to None)."""
         self._zero_gradients()
 
     def step(self):
-        self.join_prologue()                     # (no-op when the backward pass joined it, as it must)
         K.adam_step(self.flat_p, self.flat_g, self.exp_avg, self.exp_avg_sq, self.shadow, self.state, self.partial, self.lr,
                     self.betas, self.eps, self.grad_norm, self.warmup_steps)
-        self._refresh_transposed()           # in line: a captured step leaves the derived copies fresh for its next replay
-        self._began = False
+        self.refresh_derived()               # in line: a captured step leaves the derived copies fresh for its next replay
         self._touch()
 
     # -- introspection (host sync; for logging / tests only) -------------------------------------

@@ -151,8 +151,8 @@ class Trainer(object):
         return self.dp.forward_context() if self.dp is not None else contextlib.nullcontext()
 
     def _begin_step(self, zero=True):
-        """First call of a training step: clear the gradients (zero = None: only if a deferred zero_grad is pending) and, with
-        the fused optimiser, start the step prologue beside the forward pass (optim.FlatAdam.begin_step)."""
+        """First call of a training step (before the forward pass): clear the gradients if `zero` (a trainer that clears them
+        after its optimiser step, as its reference does, passes False)."""
         if isinstance(self.optimizer, FlatAdam):
             self.optimizer.begin_step(zero=zero)
         elif zero:
@@ -162,8 +162,6 @@ class Trainer(object):
         """Backward pass + (on the last micro-step of an accumulation window) the gradient exchange.
         total: the scalar loss (already divided by gradient_accumulate_steps); parts: the same loss split by the keys of
         model.dp_plan() (sum(parts) == total), used when the backward pass runs stage by stage."""
-        if isinstance(self.optimizer, FlatAdam):
-            self.optimizer.join_prologue()       # zero-fill of the gradients + refreshed weight copies: done before the first gradient
         if self.dp is not None:
             if self._capture is not None and last_micro_step:   # being captured stage by stage: the exchange runs between the replays
                 self._capture.staged_backward(self.dp, parts)
@@ -403,16 +401,15 @@ class AASVCTrainer(Trainer):
 
     def _graph_regime(self):
         """What the captured step depends on besides shapes: whether the duration loss is on, and the ROLE of the coming micro-step
-        in its accumulation window -- a deferred zero-fill is due at its start / the optimiser step follows its backward pass."""
+        in its accumulation window -- whether the optimiser step (and the zero-fill behind it) follows its backward pass."""
         last = (self.backward_steps + 1) % self.gradient_accumulate_steps == 0
-        zero_due = bool(getattr(self.optimizer, "_zero_due", False))
-        return (self.steps > self.config.get("dp_train_start_steps", 0), zero_due, last)
+        return (self.steps > self.config.get("dp_train_start_steps", 0), last)
 
     def _train_step(self, batch):
         dev = self.device
         K.reset_op_counter()
         K.advance_seed(dev)
-        self._begin_step(zero=None)             # the zero_grad deferred by the previous optimiser step runs beside this forward pass
+        self._begin_step(zero=False)            # the gradients were cleared behind the previous optimiser step (below)
         net = self._net()
         if getattr(net, "forward_sum_prefetch", 0) is None and "ForwardSumLoss" in self.criterion:
             net.forward_sum_prefetch = self.criterion["ForwardSumLoss"].prefetch     # its recursion runs beside the decoder
@@ -458,10 +455,7 @@ class AASVCTrainer(Trainer):
         if not last:
             return
         self._optimizer_step()
-        if isinstance(self.optimizer, FlatAdam):
-            self.optimizer.zero_grad(defer=True)
-        else:
-            self.optimizer.zero_grad()
+        self.optimizer.zero_grad()              # after the step, as the reference does (aas_vc.py:151-158)
         self.steps += 1
         self._check_train_finish()
 

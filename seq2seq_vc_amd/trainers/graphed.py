@@ -22,7 +22,7 @@ finished stage is issued between the replays, as bench.py does; the optimiser st
 config["hip_graph"] = "trace" never captures (the eager reference of the tests for exactly this data path).
 
 Gradient accumulation (trainers/aas_vc.py:141-149 of the reference; AASVCTrainer.GRAPH_ACCUMULATE): a MICRO-step is what gets
-captured, and its ROLE is part of the key -- (gradients cleared at its start?, optimiser step at its end?) as
+captured, and its ROLE is part of the key -- does the optimiser step follow its backward pass? -- as
 `Trainer._graph_regime()` reports it before the step runs.  An accumulation window of k micro-steps replays the "accumulate"
 graph (forward + backward into the flat gradient buffer, no zero-fill, no exchange: staged data-parallel passes run their stages
 inside this one graph) k - 1 times and the "last" graph(s) (forward + backward [+ the staged exchange] + clip / Adam / WarmupLR
@@ -55,7 +55,6 @@ class _Entry:
         self.bank = None
         self.graphs = []          # [(graph, stage index or None)]
         self.deltas = None
-        self.zero_due_after = None    # optimizer._zero_due as the captured step left it (host state a replay must reproduce)
         self.sightings = 0
 
 
@@ -199,11 +198,6 @@ class GraphedStep:
             e.bank.refresh({lname: src.tolist() for lname, src in e.lens_src.items()})
             t.steps += e.deltas[0]
             t.backward_steps += e.deltas[1]
-            if e.zero_due_after is not None:
-                # begin_step() / zero_grad(defer=True) ran as Python only at capture time: a replay must leave the flag the way the
-                # captured step did, or the next window's role key (Trainer._graph_regime) picks an accumulate graph without the
-                # zero-fill (no path sets the flag since the prologue overlap was removed)
-                t.optimizer._zero_due = e.zero_due_after
             t._check_train_finish()
             t.optimizer._touch()        # the weights change without a Python-side optimizer.step(): cached decode sessions etc. go stale
         self._replay(e)
@@ -264,8 +258,6 @@ class GraphedStep:
         torch.cuda.current_stream().wait_stream(self.stream)
         e.bank.closed = True
         e.deltas = (t.steps - before[0], t.backward_steps - before[1])
-        if hasattr(t.optimizer, "_zero_due"):
-            e.zero_due_after = bool(t.optimizer._zero_due)
 
 
 class _Capture:

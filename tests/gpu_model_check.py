@@ -1556,6 +1556,106 @@ def training_steps_bf16_transposed_shadow():
     return res
 
 
+def _derived_copies_stale(model, opt, refreshed_from_python):
+    """What is wrong with the derived weight copies FlatAdam keeps (bit-exact checks), and how many of each kind were checked.
+    refreshed_from_python: the last update ran optim.FlatAdam.refresh_derived from Python (it rewrites every registered permuted
+    copy); else it was a graph replay, which rewrites the first `covered` of them -- the others are gathered again on use."""
+    bad, seen = [], {}
+
+    def note(kind, ok, what):
+        seen[kind] = seen.get(kind, 0) + 1
+        if not ok:
+            bad.append(what)
+
+    if not torch.equal(opt.shadow, K.cast(opt.flat_p, torch.bfloat16)):
+        bad.append("shadow != cast(flat_p)")
+    carriers = [("plain matrix" if p.dim() == 2 else "1x1 convolution", p) for p in opt.params]
+    for m in model.modules():
+        carriers += list(getattr(m, "_fused", {}).items()) + [("stacked K|V", t) for k, t in getattr(m, "_src_kv_all", {}).items()]
+    for kind, t in carriers:
+        wt = getattr(t, "_s2s_bf16_t", None)
+        if wt is not None:
+            note(kind, torch.equal(wt, t._s2s_bf16.reshape(t.shape[0], -1).t()), f"{kind}: transposed shadow != shadow^T")
+    reg = opt._perm_jobs
+    for i, (w, key, buf) in enumerate(reg):
+        kind = {2: "permuted Linear", 4: "Conv2d taps"}.get(w.dim(), "Conv1d flipped" if key[1][1] < 0 else "Conv1d forward")
+        fresh = K.gather3(w.detach(), *key)
+        if refreshed_from_python or i < reg.covered:
+            note(kind, torch.equal(buf, fresh), f"{kind} {key}: registered copy {i} is stale after the refresh")
+        got = K.gather3_cached(w, *key)
+        note(kind, got is buf and torch.equal(got, fresh), f"{kind} {key}: gather3_cached returns a stale copy ({i})")
+    return bad, seen
+
+
+@case
+def derived_weight_copies_are_fresh_after_every_update():
+    """The invariant of optim.FlatAdam's derived weight copies, bit for bit, on tiny VTN in bf16: step() and refresh_shadow()
+    leave the bf16 shadow, every transposed copy and every registered permuted copy fresh; a captured step refreshes the copies
+    registered at capture time, and a copy registered later (or whose weight torch changed in place) is gathered again on use."""
+    from seq2seq_vc_amd import losses as L
+    from seq2seq_vc_amd import models as M
+    from seq2seq_vc_amd.optim import FlatAdam
+    cfg, z = load("vtn_tiny_train")
+    res, seen = [], {}
+
+    def check(point, refreshed_from_python):
+        torch.cuda.synchronize()
+        bad, kinds = _derived_copies_stale(model, opt, refreshed_from_python)
+        seen.update(kinds)
+        res.append((not bad, f"{point}: {sum(kinds.values())} derived copies fresh {bad[:3]}"))
+
+    try:
+        Fn.set_compute_dtype(torch.bfloat16)
+        K.manual_seed(7)
+        model = M.VTN(**model_cfg(cfg))
+        model.load_state_dict(sd_of(z))
+        model.to(DEV).train()
+        for m in model.modules():
+            if hasattr(m, "dropout_rate"):
+                m.dropout_rate = 0.0
+        opt = FlatAdam(model, lr=1e-3, grad_norm=1.0, warmup_steps=10, bf16_shadow=True)
+        crit = L.Seq2SeqLoss(10.0)
+        t = lambda k: torch.from_numpy(z[k])
+        xs, ys, labels = t("in.xs").to(DEV), t("in.ys").to(DEV), t("in.labels").to(DEV)
+        for step in range(2):
+            K.reset_op_counter()
+            opt.zero_grad()
+            o = model(xs, t("in.ilens"), ys, labels, t("in.olens"))
+            l1, bce = crit(o[0], o[1], o[2], o[3], o[4], o[5])
+            (l1 + bce).backward()
+            Fn.side_join()
+            opt.step()
+            check(f"eager step {step + 1}", True)
+        n_before = len(opt._perm_jobs)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            opt.step()                      # (the gradients of the last backward pass stay: every replay moves the weights)
+        res.append((opt._perm_jobs.covered == n_before, f"the captured refresh covers the {n_before} copies registered so far"))
+        for replay in range(2):
+            before = opt.flat_p.clone()
+            g.replay()
+            check(f"captured step, replay {replay + 1}", False)
+            res.append((not torch.equal(before, opt.flat_p), f"replay {replay + 1} changed the weights"))
+        conv = next(w for w, key, _ in opt._perm_jobs if w.dim() == 3)
+        Cout, Cin, ks = conv.shape
+        late = K.gather3_cached(conv, (Cout, ks, Cin), (Cin * ks, 1, ks), 0, torch.float32)      # a dtype not used before
+        res.append((len(opt._perm_jobs) == n_before + 1 and opt._perm_jobs[-1][2] is late, "a copy registered after the capture"))
+        g.replay()
+        check("replay after a late registration", False)
+        model.load_state_dict(sd_of(z))
+        opt.refresh_shadow()
+        check("load_state_dict + refresh_shadow", True)
+        name, first = next(iter(model.named_parameters()))
+        res.append((torch.equal(first.detach().cpu(), sd_of(z)[name]), f"the loaded weights are in place ({name})"))
+    finally:
+        Fn.set_compute_dtype(torch.float32)
+    need = ("plain matrix", "w_qkv", "w_kv", "stacked K|V", "Conv1d forward", "Conv1d flipped", "Conv2d taps", "permuted Linear")
+    missing = [k for k in need if not seen.get(k)]
+    res.append((not missing and len(opt._perm_jobs) >= 4, f"kinds of derived copies checked: {seen}; missing {missing}"))
+    return res
+
+
 
 # =================================================================================================
 # round 2: AASVC.inference, full-width single layers, and the BASELINE configurations at full size

@@ -418,26 +418,79 @@ def test_lens_bank_tracks_the_cropped_length_the_reference_computes_on():
     assert plain.host == (24, 15, 21) and plain.ext is None
 
 
-def test_perm_registry_host_logic():
-    """ops.kernels.PermRegistry (state of the step prologue / derived weight copies): the bookkeeping that needs no GPU -- a
-    consumer that arrives while a refresh is due runs it first, join() forgets the events."""
-    from seq2seq_vc_amd.ops import kernels as K
-    reg = K.PermRegistry()
-    calls = []
+# optim.plan_layout on the committed fixtures' models, built on the CPU: (fixture, model class, trainable tensors, sum of their
+# elements, flat element count, contiguous Q|K|V groups, contiguous decoder K|V stacks).  The counts are part of the assertion: a
+# planner that silently stops fusing must fail.
+LAYOUTS = [("vtn_tiny_train", "VTN", 119, 128646, 130624, 4, 1),
+           ("vtn_conformer_tiny_train", "VTN", 160, 146565, 149376, 4, 1),
+           ("tts_tiny_train", "TransformerTTS", 114, 95204, 97088, 4, 1),
+           ("aasvc_tiny_train", "AASVC", 473, 667808, 678016, 4, 0),
+           ("fs2vc_tiny_train", "FastSpeechVC", 191, 178641, 182400, 4, 0)]
 
-    def refresh():
-        reg.due = False
-        calls.append(1)
 
-    reg.refresh = refresh
-    reg.sync("perm")                       # nothing due, no events: no-op
-    assert calls == []
-    reg.due = True
-    reg.sync()                             # due: refreshed here, once
-    reg.sync("perm")
-    assert calls == [1] and not reg.due
-    reg.join()
-    assert reg.ev_perm is None and reg.ev_all is None and reg.waited == set()
+@pytest.mark.parametrize("fixture,cls,n_tensors,n_elements,numel,n_groups,n_stacks", LAYOUTS, ids=[row[0] for row in LAYOUTS])
+def test_plan_layout_on_fixture_models(fixture, cls, n_tensors, n_elements, numel, n_groups, n_stacks):
+    """The flat layout (packed projections, flat gradient slots, data-parallel buckets and checkpoints hang on it) is pure host
+    arithmetic: checked here on CPU models, no allocation."""
+    import json
+    from seq2seq_vc_amd import models as M
+    from seq2seq_vc_amd.optim import plan_layout
+    z = np.load(os.path.join(ROOT, "tests", "golden", fixture + ".npz"))
+    cfg = {k: v for k, v in json.loads(bytes(z["__cfg__"]).decode()).items() if not k.startswith("__")}
+    model = getattr(M, cls)(**cfg)
+    lay = plan_layout(model)
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    # every trainable parameter exactly once
+    assert len(lay.params) == len(lay.offsets) == len(trainable) == n_tensors
+    assert sorted(map(id, lay.params)) == sorted(map(id, trainable))
+    assert sum(p.numel() for p in lay.params) == n_elements
+    assert lay.numel == numel and lay.numel % 64 == 0
+    assert (len(lay.groups), len(lay.stacks)) == (n_groups, n_stacks)
+    off = {id(p): o for p, o in zip(lay.params, lay.offsets)}
+    # flat order, no overlap; 64-aligned except tight members (non-first weights / biases of a run), which start where their
+    # predecessor ends
+    may_be_tight = {id(p) for r in lay.groups + lay.stacks for p in r["w"][1:] + r["b"][1:]}
+    end = 0
+    for p, o in zip(lay.params, lay.offsets):
+        assert o >= end
+        assert o % 64 == 0 or (id(p) in may_be_tight and o == end)
+        end = o + p.numel()
+    assert end <= lay.numel
+    for g in lay.groups:                       # [Wq;Wk;Wv] is one (3D, D) matrix, [bq;bk;bv] one vector
+        m, D = g["module"], g["w"][0].shape[0]
+        assert g["w"] == [m.linear_q.weight, m.linear_k.weight, m.linear_v.weight]
+        assert [off[id(w)] for w in g["w"]] == [off[id(g["w"][0])] + i * D * D for i in range(3)]
+        assert [off[id(b)] for b in g["b"]] == [off[id(g["b"][0])] + i * D for i in range(3)]
+    for st in lay.stacks:                      # one run in k_1, v_1, k_2, v_2, ... order
+        D = st["w"][0].shape[0]
+        assert st["w"] == [w for m in st["mods"] for w in (m.linear_k.weight, m.linear_v.weight)]
+        assert st["b"] == [b for m in st["mods"] for b in (m.linear_k.bias, m.linear_v.bias)]
+        assert st["mods"] == [layer.src_attn for layer in st["decoder"].decoders]
+        assert [off[id(w)] for w in st["w"]] == [off[id(st["w"][0])] + i * D * D for i in range(len(st["w"]))]
+        assert [off[id(b)] for b in st["b"]] == [off[id(st["b"][0])] + i * D for i in range(len(st["b"]))]
+    # transposed-shadow table: plain matrices keep their offset; the extras (w_qkv and w_kv per group, the stacked K|V per
+    # decoder) start at the flat element count, are 64-aligned and disjoint
+    plain = [e for e in lay.t_table if isinstance(e[4], torch.Tensor)]
+    extras = [e for e in lay.t_table if not isinstance(e[4], torch.Tensor)]
+    matrices = [p for p in lay.params if p.dim() == 2 or (p.dim() == 3 and p.shape[-1] == 1)]
+    assert [id(e[4]) for e in plain] == [id(p) for p in matrices] and plain
+    for so, do, rows, cols, p in plain:
+        assert so == do == off[id(p)] and (rows, cols) == tuple(p.shape[:2])
+    assert len(extras) == 2 * n_groups + n_stacks
+    assert sorted(e[4][2] for e in extras) == sorted(["w_qkv", "w_kv"] * n_groups + ["w"] * n_stacks)
+    end = lay.numel
+    for so, do, rows, cols, (holder, attr, key) in extras:
+        assert do == end and do % 64 == 0
+        end = do + (rows * cols + 63) // 64 * 64
+        run = next(r for r in lay.groups + lay.stacks if holder is r.get("module", r.get("decoder")))
+        D = run["w"][0].shape[0]
+        assert cols == D and (so, rows) == {"w_qkv": (run["ow"], 3 * D), "w_kv": (run["ow"] + D * D, 2 * D),
+                                             "w": (run["ow"], len(run["w"]) * D)}[key]
+    assert lay.t_numel == end
+    assert not hasattr(model, "_fused") and all(not hasattr(m, "_fused") for m in model.modules())     # planning attaches nothing
+    bare = plan_layout(model, fuse_qkv=False, transposed=False)
+    assert (bare.groups, bare.stacks, bare.t_table, bare.t_numel) == ([], [], [], bare.numel)
+    assert [id(p) for p in bare.params] == [id(p) for p in trainable] and all(o % 64 == 0 for o in bare.offsets)
 
 
 def _run_bench(args, env_extra=None, timeout=240):
