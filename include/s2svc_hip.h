@@ -761,6 +761,33 @@ int s2svc_gl_analyse(int B, int Tmax, int n_fft, int hop, int reflect, const flo
 int s2svc_gl_ola(int B, int Tmax, int n_fft, int hop, const float* frames, const int32_t* lens, const float* tables, float* y,
                  void* stream);
 
+/* ========================================================================================== */
+/* Urhythmic: segmentation search and time stretcher.                                         */
+/* replaces: urhythmic/segmenter.py:138-191 (_segment / _backtrack, numba-JIT on the host over */
+/* a dense (T, T, K) table, and cluster_merge), urhythmic/stretcher.py:23-71 (F.interpolate    */
+/* per segment + torch.cat).  LIMITS: K <= 256 units, Tmax <= 4096 frames, B <= 65535.         */
+/* Frames t >= lens[b] are never read (log_probs or workspace); inputs are assumed finite.     */
+/* ========================================================================================== */
+/* workspace of the two launches below: max_k and argmax_k of every span's running sum, [b][end frame][start frame] */
+int64_t s2svc_useg_ws_bytes(int B, int Tmax, int K);
+/* log_probs (B, Tmax, K) fp32 -> ws: for 0 <= a <= e < lens[b] the fp32 running sums r_a,e[k] = r_a,e-1[k] + log_probs[e,k] (r_a,a =
+   log_probs[a]; sequential, one rounding each), their maximum over k and the smallest k that attains it. */
+int s2svc_useg_spans(int B, int Tmax, int K, const float* log_probs, const int32_t* lens, void* ws, void* stream);
+/* The dynamic programme of _segment (the running maximum rounded to float32 after every update; gamma * s and the comparison in
+   float64), the backtrack and, with labels ([K] int32 unit -> cluster; NULL: none of the last three outputs is written), cluster_merge.
+   codes (B, Tmax): unit of every frame; boundaries (B, Tmax + 1): ascending from 0, nseg[b] + 1 of them; alpha (B, Tmax + 1) fp32 and
+   P (B, Tmax + 1, 2) (start frame, unit) may be NULL; clusters (B, Tmax), cboundaries (B, Tmax + 1), ncl (B).  Everything past a
+   row's own entries is written as zero; a row of length 0 has nseg = ncl = 0 and boundaries [0]. */
+int s2svc_useg_search(int B, int Tmax, double gamma, const int32_t* lens, const void* ws, const int32_t* labels, int32_t* codes,
+                      int32_t* boundaries, int32_t* nseg, float* alpha, int32_t* P, int32_t* clusters, int32_t* cboundaries,
+                      int32_t* ncl, void* stream);
+/* Segment-wise linear resampling (F.interpolate(mode="linear", align_corners=False) of every segment on its own, concatenated).
+   x element (b, t, c) at b*sb + t*st + c*sc, t < N, dtype 0 / 1; seg (B, Smax, 4) int32 = (source start, source length, target length,
+   exclusive prefix sum of the target lengths), nsegs (B); target lengths are positive.  out (B, Nmax, C) fp32, zero past the row's
+   own frames.  scale > 0: the source step of every segment (1 / scale_factor, as torch uses it); otherwise source / target length. */
+int s2svc_useg_stretch(int dtype, int B, int N, int C, const void* x, int64_t sb, int64_t st, int64_t sc, const int32_t* seg,
+                       const int32_t* nsegs, int Smax, int Nmax, float scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
