@@ -421,6 +421,8 @@ int64_t s2svc_mas_ws_bytes(int B, int Tf, int Tx);
 /* path (B,Tf) int32 (-1 beyond feat_len), ds (B,Tx) fp32 durations, binmean (B) = mean_t log_p[t, path[t]] */
 int s2svc_mas(int B, int Tf, int Tx, const float* log_p_attn, const int32_t* text_lens, const int32_t* feat_lens,
               int32_t* path, float* ds, float* binmean, void* ws, void* stream);
+/* dlogp[b, t, path[b, t]] += -gout / (B * min(feat_lens[b], Tf)) for every path entry >= 0; B == 0 returns cleanly, Tf or Tx <= 0 is
+   refused, as in s2svc_mas */
 int s2svc_mas_binloss_bwd(int B, int Tf, int Tx, const int32_t* path, const int32_t* feat_lens, const float* gout,
                           float* dlogp, void* stream);
 int s2svc_gauss_upsample_probs(int dtype, int B, int Tf, int Tx, const float* ds, const int32_t* text_lens,
@@ -430,7 +432,9 @@ int s2svc_gauss_upsample_probs(int dtype, int B, int Tf, int Tx, const float* ds
    torch.repeat_interleave + pad_list): frame i of utterance b is repeated ds[b, i] times.
      _index: start (B,Tx) = exclusive prefix sums of ds, idx (B,Tout) = source frame of every output frame (-1 = padding),
              total (B) = sum of ds (may be NULL);   _fwd: y (B,Tout,D) = x[b, idx] or pad_value;
-     _bwd:   dx (B,Tx,D) = sum of dy over each frame's run (fixed order, no atomics). */
+     _bwd:   dx (B,Tx,D) = sum of dy over each frame's run (fixed order, no atomics).
+     Tout = 0 is a valid empty output: _index writes start / total only, _fwd returns without a launch, _bwd writes dx = 0
+     (idx, y and dy of an empty output may be NULL). */
 int s2svc_length_regulate_index(int B, int Tx, int Tout, const int32_t* ds, int32_t* start, int32_t* idx, int32_t* total,
                                 void* stream);
 int s2svc_length_regulate_fwd(int dtype, int B, int Tx, int Tout, int D, const void* x, const int32_t* idx, float pad_value,
@@ -448,6 +452,9 @@ int s2svc_attn_durations(int NH, int Tf, int Tx, const float* att, int64_t* dura
 /* replaces: losses/seq2seq_loss.py:30-59, losses/l1_loss.py:22-49, guided_attention_loss.py: */
 /* 142-165, forward_sum_loss.py:26-116 (F.ctc_loss loop + scipy beta-binomial prior).          */
 /* ========================================================================================== */
+/* Empty problems are refused (rc -1, nothing launched or written) by each forward and its backward alike: B, Tm or D <= 0 for the
+   sequence loss; B, H, To or Ti <= 0 or sigma <= 0 for the guided attention loss.  The guided attention kernels take ilens[b] > Ti /
+   olens[b] > To as Ti / To, in the weights as in the count. */
 int s2svc_seq_loss_fwd(int dtype, int B, int Tm, int D, const void* after, const void* before, const void* logits,
                        const float* ys, const float* labels, const int32_t* olens, float pos_weight, float* partial,
                        float* out, void* stream);
@@ -635,6 +642,8 @@ int s2svc_decode_emit_advance(int dtype, int B, int r, int odim, const void* fea
 /* Optimiser: grad-norm -> clip -> WarmupLR -> Adam (+ bf16 shadow) over one flat buffer       */
 /* replaces: trainers/ar_vc.py:99-107 (clip_grad_norm_, Adam.step, scheduler.step),            */
 /* schedulers/warmup_lr.py:54-61.  state: 4 device floats {step, lr, grad_norm, clip_coef}.    */
+/* A refused call (rc -1: bad arguments, buffers not 16-byte aligned) launches nothing and    */
+/* leaves state, params and both moments as they were.                                        */
 /* ========================================================================================== */
 int s2svc_adam_step(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq, void* bf16_shadow,
                     float beta1, float beta2, float eps, float max_norm, float base_lr, float warmup_steps,

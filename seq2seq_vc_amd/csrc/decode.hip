@@ -46,6 +46,8 @@ template <typename T> struct VLoad<T, 1> {
 // One workgroup per (utterance, head).  Optional append of the new key/value row at *pos; scores: 4 lanes per
 // key, 64 keys per pass, 16-byte row loads all in flight at once; softmax statistics by one wavefront; context:
 // (d_k / VEC) column chunks x S key-splits of threads accumulate P.V partials, summed through LDS in fixed order.
+// A row with no key (klen[b] <= 0) visits nothing: the sum of exponentials is 0 and inv = 1 / 0 is never multiplied, so its
+// context is 0 and its attention row is 0 (all finite); klen[b] > Tk is clamped to Tk.  tests/gpu_step_kernel_check.py pins both.
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void decode_attn_kernel(int H, int dk, const T* __restrict__ q, int64_t ldq, T* __restrict__ kc,
                                                           T* __restrict__ vc, int64_t ldt, int64_t cbs, const T* __restrict__ knew,

@@ -151,8 +151,9 @@ extern "C" int s2svc_length_regulate_index(int B, int Tx, int Tout, const int32_
 
 extern "C" int s2svc_length_regulate_fwd(int dtype, int B, int Tx, int Tout, int D, const void* x, const int32_t* idx, float pad_value,
                                          void* y, void* stream) {
-  S2S_REQUIRE(B > 0 && Tx > 0 && D > 0 && x && idx && y, "length_regulate_fwd: bad args");
-  if (Tout == 0) return 0;
+  S2S_REQUIRE(B > 0 && Tx > 0 && D > 0 && Tout >= 0, "length_regulate_fwd: bad args");
+  if (Tout == 0) return 0;                 // nothing to write: idx and y of an empty output have no storage to point at
+  S2S_REQUIRE(x && idx && y, "length_regulate_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * Tout * D;
   const bool al = ((uintptr_t)x) % 16 == 0 && ((uintptr_t)y) % 16 == 0;
@@ -173,7 +174,8 @@ extern "C" int s2svc_length_regulate_fwd(int dtype, int B, int Tx, int Tout, int
 
 extern "C" int s2svc_length_regulate_bwd(int dtype, int B, int Tx, int Tout, int D, const void* dy, const int32_t* start, const int32_t* ds,
                                          void* dx, void* stream) {
-  S2S_REQUIRE(B > 0 && Tx > 0 && D > 0 && dy && start && ds && dx, "length_regulate_bwd: bad args");
+  // Tout == 0: every run is empty, dx = 0, and dy (an empty tensor, never read) may be NULL
+  S2S_REQUIRE(B > 0 && Tx > 0 && D > 0 && Tout >= 0 && (dy || Tout == 0) && start && ds && dx, "length_regulate_bwd: bad args");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * Tx * D;
   if (dtype == S2S_F32)

@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256) void ga_loss_fwd_kernel(int B, int H, int To, 
     const int64_t r = i / Ti;
     const int to = (int)(r % To);
     const int b = (int)(r / To / H);
-    const int il = ilens[b], ol = olens[b];
+    const int il = ilens[b] < Ti ? ilens[b] : Ti, ol = olens[b] < To ? olens[b] : To;   // clamped, as ga_loss_final_kernel counts them
     if (ti < il && to < ol) {
       const float d = (float)ti / (float)il - (float)to / (float)ol;
       a += (1.f - expf(-(d * d) / (2.f * sigma * sigma))) * ldf(att + i);
@@ -155,7 +155,7 @@ __global__ void ga_loss_bwd_kernel(int B, int H, int To, int Ti, const int32_t* 
     const int64_t r = i / Ti;
     const int to = (int)(r % To);
     const int b = (int)(r / To / H);
-    const int il = ilens[b], ol = olens[b];
+    const int il = ilens[b] < Ti ? ilens[b] : Ti, ol = olens[b] < To ? olens[b] : To;   // clamped, as ga_loss_final_kernel counts them
     float g = 0.f;
     if (ti < il && to < ol) {
       const float d = (float)ti / (float)il - (float)to / (float)ol;
@@ -173,6 +173,7 @@ inline int red_blocks(int64_t n) {
 }  // namespace
 
 // partial: >= 3*1024 floats.  out: 3 floats {l1, bce, valid_frames}.  after/logits may be NULL.
+// Empty problems (B, Tm or D <= 0) are REFUSED by the forward and the backward launcher alike ("bad args", nothing launched).
 extern "C" int s2svc_seq_loss_fwd(int dtype, int B, int Tm, int D, const void* after, const void* before,
                                   const void* logits, const float* ys, const float* labels, const int32_t* olens,
                                   float pos_weight, float* partial, float* out, void* stream) {
@@ -195,6 +196,9 @@ extern "C" int s2svc_seq_loss_bwd(int dtype, int B, int Tm, int D, const void* a
                                   const void* logits, const float* ys, const float* labels, const int32_t* olens,
                                   float pos_weight, const float* stats, const float* g_l1, const float* g_bce,
                                   void* d_after, void* d_before, void* d_logits, void* stream) {
+  // an empty problem is refused, as in s2svc_seq_loss_fwd (a mean over no frame is not a loss); nothing is launched or written
+  S2S_REQUIRE(B > 0 && Tm > 0 && D > 0 && before && ys && olens && stats && d_before, "seq_loss_bwd: bad args");
+  S2S_REQUIRE((!d_after || after) && (!d_logits || (logits && labels)), "seq_loss_bwd: a gradient without its input");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * Tm * D;
   int nb = (int)((n + 255) / 256);
@@ -212,9 +216,14 @@ extern "C" int s2svc_seq_loss_bwd(int dtype, int B, int Tm, int D, const void* a
 }
 
 // partial >= 1024 floats; out: 2 floats {loss, valid_count}
+// Empty problems (B, H, To or Ti <= 0) and sigma <= 0 are REFUSED by the forward and the backward launcher alike (nothing launched).
+// A length above Ti / To counts as Ti / To, in the weights as in the count.
 extern "C" int s2svc_guided_attn_loss_fwd(int dtype, int B, int H, int To, int Ti, const void* att, const int32_t* ilens,
                                           const int32_t* olens, float sigma, float alpha, float* partial, float* out,
                                           void* stream) {
+  // an empty attention map is refused (its mean would be 0 / 0); nothing is launched or written
+  S2S_REQUIRE(B > 0 && H > 0 && To > 0 && Ti > 0 && att && ilens && olens && partial && out, "guided_attn_loss_fwd: bad args");
+  S2S_REQUIRE(sigma > 0.f, "guided_attn_loss_fwd: sigma must be positive");
   hipStream_t st = (hipStream_t)stream;
   const int nb = red_blocks((int64_t)B * H * To * Ti);
   if (dtype == S2S_F32)
@@ -230,6 +239,9 @@ extern "C" int s2svc_guided_attn_loss_fwd(int dtype, int B, int H, int To, int T
 extern "C" int s2svc_guided_attn_loss_bwd(int dtype, int B, int H, int To, int Ti, const int32_t* ilens,
                                           const int32_t* olens, float sigma, float alpha, const float* stats,
                                           const float* gout, void* datt, void* stream) {
+  // refused exactly where s2svc_guided_attn_loss_fwd refuses; nothing is launched or written
+  S2S_REQUIRE(B > 0 && H > 0 && To > 0 && Ti > 0 && ilens && olens && stats && datt, "guided_attn_loss_bwd: bad args");
+  S2S_REQUIRE(sigma > 0.f, "guided_attn_loss_bwd: sigma must be positive");
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = (int64_t)B * H * To * Ti;
   int nb = (int)((n + 255) / 256);

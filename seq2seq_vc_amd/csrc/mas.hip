@@ -234,7 +234,10 @@ extern "C" int s2svc_mas(int B, int Tf, int Tx, const float* log_p_attn, const i
 
 extern "C" int s2svc_mas_binloss_bwd(int B, int Tf, int Tx, const int32_t* path, const int32_t* feat_lens,
                                      const float* gout, float* dlogp, void* stream) {
+  // as s2svc_mas: an empty batch returns cleanly, a shape without frames or tokens is refused; nothing is launched in either case
+  S2S_REQUIRE(B >= 0 && Tf > 0 && Tx > 0, "mas_binloss_bwd: bad shape");
   if (B == 0) return 0;
+  S2S_REQUIRE(path && feat_lens && gout && dlogp, "mas_binloss_bwd: bad args");
   const int64_t n = (int64_t)B * Tf;
   int blocks = (int)((n + 255) / 256);
   if (blocks > 2048) blocks = 2048;

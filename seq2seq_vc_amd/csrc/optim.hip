@@ -136,10 +136,15 @@ __global__ void adam_update_kernel(int64_t n, float* __restrict__ p, const float
 }  // namespace
 
 // partial: >= 1024 doubles.  state: 4 floats in device memory (see adam_prepare_kernel).
+// A refused call (bad arguments, misaligned buffers) launches nothing: state, params and both moments are left as they were.
 extern "C" int s2svc_adam_step(int64_t n, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
                                void* bf16_shadow, float beta1, float beta2, float eps, float max_norm, float base_lr,
                                float warmup_steps, double* partial, float* state, void* stream) {
   S2S_REQUIRE(n > 0 && params && grads && exp_avg && exp_avg_sq && partial && state, "adam_step: bad args");
+  // every argument check comes before the first launch: adam_prepare_kernel advances state[0] and overwrites lr / norm / coef, so a
+  // call refused after it would have moved the step counter without an update
+  S2S_REQUIRE(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0 &&
+                  (!bf16_shadow || ((uintptr_t)bf16_shadow) % 8 == 0), "adam_step: 16-byte aligned buffers");
   hipStream_t st = (hipStream_t)stream;
   int nb = (int)((n + 255) / 256);
   if (nb > 1024) nb = 1024;
@@ -147,8 +152,6 @@ extern "C" int s2svc_adam_step(int64_t n, float* params, const float* grads, flo
   S2S_CHECK_LAUNCH("sumsq_kernel");
   hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, st, nb, partial, max_norm, base_lr, warmup_steps, state);
   S2S_CHECK_LAUNCH("adam_prepare_kernel");
-  S2S_REQUIRE(((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) % 16 == 0 &&
-                  (!bf16_shadow || ((uintptr_t)bf16_shadow) % 8 == 0), "adam_step: 16-byte aligned buffers");
   // one thread per four parameters, no grid-stride cap: measured on 157.5 M / 30.5 M parameters (sumsq + prepare + update,
   // one box) 1017 / 183 us against 1150 / 190 with 4096 blocks striding and 1085 / 199 for the one-parameter-per-thread form
   const int64_t ub = (n / 4 + 255) / 256 > 0 ? (n / 4 + 255) / 256 : 1;

@@ -1,5 +1,9 @@
-"""Kernel-level parity sweep (runs on the GPU box): every launcher in seq2seq_vc_amd.ops.kernels is
-compared with a plain fp32 torch formulation of the same op.  Used two ways:
+"""Kernel-level parity sweep (runs on the GPU box): the GEMM, normalisation, attention, element-wise, front-end and fused decode-tail
+launchers of seq2seq_vc_amd.ops.kernels are compared with a plain fp32 torch formulation of the same op.  Not every launcher is
+checked HERE: the decode step, the sequence / guided-attention losses, the length regulator, the fused Adam step and the glue kernels
+are in tests/gpu_step_kernel_check.py, the AAS-VC / Conformer kernels in tests/gpu_kernel_check_aas.py, the vocoders and urhythmic in
+their own modules; tests/test_step_kernels_host.py::test_every_launcher_has_a_kernel_level_check holds the ledger of which module
+reaches which entry point of include/s2svc_hip.h and fails when a launcher has none.  Used two ways:
   * `python tests/gpu_kernel_check.py` prints a PASS/FAIL table for all cases and never stops early
     (one gpurun round trip shows every broken kernel);
   * tests/test_gpu_kernels.py imports CASES and turns each into a `@pytest.mark.gpu` test.
