@@ -255,7 +255,8 @@ int s2svc_bn_bwd(int dtype, int64_t rows, int C, const void* dy, const void* x, 
 /* (rel_shift new / legacy), :278-303 ((ac+bd)/sqrt(d_k)).  rel_mode 0 none, 1 new, 2 legacy. */
 /* ========================================================================================== */
 /* score / probability rows are `ld` >= T2 elements apart (rows padded to a vector multiple); pad columns are written as 0; */
-/* rows of the relative-position term bd / dbd (length Lp) are `ldb` >= Lp elements apart (dbd pad columns are written as 0) */
+/* rows of the relative-position term bd / dbd (length Lp) are `ldb` >= Lp elements apart (dbd pad columns are written as 0); */
+/* the forward and the backward both refuse ld < T2 and ldb < Lp before any launch                                          */
 int s2svc_attn_softmax_fwd(int dtype, int B, int H, int T1, int T2, int ld, const float* scores, const float* bd, int Lp,
                            int ldb, int rel_mode, float scale, const int32_t* klen, int causal, float drop_p,
                            const uint64_t* seed_base, uint64_t seed_off, void* attn, void* pdrop, void* stream);
@@ -482,7 +483,8 @@ int s2svc_betabinom_prior(int B, int Tf, int Tx, const int32_t* text_lens, const
 /* forward (scores, mask, softmax, dropout, P.V; writes the attention map) and one backward.   */
 /* replaces: modules/transformer/attention.py:63-111 for VTN's shapes (T = 63/64, d_k = 96).   */
 /* q/k/v/out/grads: element [b*bs + t*ld + h*dk + d] (bf16; slices of packed projections are   */
-/* fine); attn / dattn: (B, H, T1, ld) bf16, pad columns >= T2 written as 0.                   */
+/* fine); attn / dattn: (B, H, T1, ld) bf16, T2 <= ld (forward: ld <= 64), pad columns [T2, ld) */
+/* written as 0.                                                                              */
 /* ========================================================================================== */
 int s2svc_attn_fused_supported(int dtype, int T1, int T2, int dk);
 int s2svc_attn_fused_fwd(int B, int H, int T1, int T2, int dk, const void* q, int64_t ldq, int64_t qbs, const void* k, int64_t ldk,

@@ -6,7 +6,10 @@
 // 128 (b, h) pairs) every one of those is a ~7 us launch-bound kernel.  Here forward and backward are ONE launch
 // each: K / V (and their transposes, where an MFMA operand needs the other index contiguous) are staged in LDS
 // once per workgroup, each wavefront owns 16 query rows, softmax runs on the MFMA accumulator layout with 16-lane
-// shuffles, P goes to HBM only as the API-visible attention map (pre-dropout, bf16, rows padded to `ld`).
+// shuffles, P goes to HBM only as the API-visible attention map (pre-dropout, bf16, rows padded to `ld`: the forward writes the
+// columns below 64 only, pad columns [T2, ld) as 0, so its launcher refuses ld > 64).
+// Roundings to bf16: the stored map; its dropped copy bf16(stored map * keep), which is what meets V (and, in the backward, dO);
+// dS before the dQ / dK products; the stored outputs.  Everything else is fp32.
 // Dropout masks are functions of (seed, element index in the attention map) -- the backward regenerates them.
 #include "common.h"
 #include "../../include/s2svc_hip.h"
@@ -339,7 +342,8 @@ extern "C" int s2svc_attn_fused_fwd(int B, int H, int T1, int T2, int dk, const 
                                     float scale, float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* attn, int ld,
                                     void* out, int64_t ldo, int64_t obs, void* stream) {
   S2S_REQUIRE(s2svc_attn_fused_supported(S2S_BF16, T1, T2, dk), "attn_fused_fwd: unsupported shape (bf16, T <= 64, d_k in {32,64,96,128})");
-  S2S_REQUIRE(ld >= T2 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && qbs % 8 == 0 && kbs % 8 == 0 && vbs % 8 == 0,
+  S2S_REQUIRE(ld >= T2 && ld <= 64, "attn_fused_fwd: the map's row pitch ld must be in [T2, 64]");
+  S2S_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && qbs % 8 == 0 && kbs % 8 == 0 && vbs % 8 == 0,
               "attn_fused_fwd: strides must be multiples of 8 elements");
   S2S_REQUIRE(((uintptr_t)q) % 16 == 0 && ((uintptr_t)k) % 16 == 0 && ((uintptr_t)v) % 16 == 0, "attn_fused_fwd: 16-byte aligned q/k/v");
   if (B == 0) return 0;
@@ -360,7 +364,8 @@ extern "C" int s2svc_attn_fused_bwd(int B, int H, int T1, int T2, int dk, const 
                                     const uint64_t* seed_base, uint64_t seed_off, void* dq, int64_t lddq, int64_t dqbs, void* dk_out,
                                     int64_t lddk, int64_t dkbs, void* dv, int64_t lddv, int64_t dvbs, void* stream) {
   S2S_REQUIRE(s2svc_attn_fused_supported(S2S_BF16, T1, T2, dk), "attn_fused_bwd: unsupported shape (bf16, T <= 64, d_k in {32,64,96,128})");
-  S2S_REQUIRE(ld >= T2 && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && qbs % 8 == 0 && kbs % 8 == 0 && vbs % 8 == 0 &&
+  S2S_REQUIRE(ld >= T2, "attn_fused_bwd: the map's row pitch ld must be >= T2");
+  S2S_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && qbs % 8 == 0 && kbs % 8 == 0 && vbs % 8 == 0 &&
               obs % 8 == 0, "attn_fused_bwd: strides must be multiples of 8 elements");
   S2S_REQUIRE(((uintptr_t)q) % 16 == 0 && ((uintptr_t)k) % 16 == 0 && ((uintptr_t)v) % 16 == 0 && ((uintptr_t)dout) % 16 == 0,
               "attn_fused_bwd: 16-byte aligned q/k/v/dout");

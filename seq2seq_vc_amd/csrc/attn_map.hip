@@ -15,6 +15,9 @@
 // slice; the scores meet in an fp32 LDS tile, one wave per row does the softmax (or its backward), the bf16 rows leave in 16-byte stores.
 // DK2 in {64, 96, 128}: the finished bf16 tile is then the A operand of a second product with the head's (keys x d_k) matrix, which was
 // fetched into registers under the row pass and is laid over the dead tile for `ds_read_b64_tr_b16` (see below).
+// Roundings to bf16: the stored map; its dropped copy bf16(fp32 probability * keep) (as softmax.hip forms it: NOT from the rounded map,
+// unlike attn_fused.hip / relattn.hip); the tile (dropped copy, or the map without dropout; dS in the backward) before the second
+// product; the stored outputs.  Everything else is fp32.
 // Same output layout ((B, H, T1, ld), ld = T2 rounded up to 8, pad columns zero) and the same dropout masks (a function of the seed and
 // the element index in that layout) as softmax.hip / attn_fused.hip: forward and backward may come from different kernel families.
 #include "common.h"
@@ -278,7 +281,9 @@ __global__ __launch_bounds__(64 * NW) void attn_map_kernel(const am_args a) {
         uint32_t* rowA = reinterpret_cast<uint32_t*>(S + il * SP);   // (LDS operations of one wave execute in order: the row was read above)
 #pragma unroll
         for (int c = 0; c < CP; ++c)
-          rowA[lane + 64 * c] = f2bf2(pr[2 * c] * (tt[2 * c] - dot) * a.scale, pr[2 * c + 1] * (tt[2 * c + 1] - dot) * a.scale);
+          // (+ 0.f: where the stored map is +0 -- masked positions, pad columns -- the product is -0 whenever its other factor is negative; the sum
+          //  with +0 is +0 bit for bit, and every other value is unchanged)
+          rowA[lane + 64 * c] = f2bf2(pr[2 * c] * (tt[2 * c] - dot) * a.scale + 0.f, pr[2 * c + 1] * (tt[2 * c + 1] - dot) * a.scale + 0.f);
       }
       if (g + 1 < NG) {
 #pragma unroll

@@ -21,6 +21,8 @@
 // registers: the compiler waits for ALL outstanding loads at the top of the loop, so every slice paid a trip to L2 -- 2 us per slice.)
 // The probabilities leave through an LDS image of the tile in 16-byte stores.
 // Dropout masks are functions of (seed, element index of the attention map), the same function the separate kernels use.
+// Roundings to bf16: qu and qv (stored, then read back as the operands of both score products), the stored map, and its dropped copy
+// bf16(stored map * keep).  Everything else is fp32.
 #include "common.h"
 #include "../../include/s2svc_hip.h"
 

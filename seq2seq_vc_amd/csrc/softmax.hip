@@ -1,6 +1,7 @@
 // Attention probability kernels: scale + (relative-position shift) + length/causal masking + softmax
 // + re-mask + dropout, one wavefront per score row, reductions by wave shuffles; and the matching
 // backward.  Masks are never materialised: kernels take per-batch key lengths and a causal flag.
+// Roundings (bf16 maps only): the stored map, its dropped copy = round(fp32 probability * keep), the stored dscores / dbd.
 //
 // reference: modules/transformer/attention.py:63-93 (forward_attention), :237-260 (rel_shift, new),
 //            :142-160 (rel_shift, legacy), :278-303 (matrix_ac + matrix_bd) / sqrt(d_k).
@@ -124,7 +125,8 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(int B, int H, int T1, 
     const int64_t o = row * ld + j;
     float m = p > 0.f ? dropout_scale(seed, (uint64_t)o, p, inv_keep) : 1.f;
     float pr = ldf(attn + o);
-    float ds = pr * (dp[o] * m + (dattn ? ldf(dattn + o) : 0.f) - dot) * scale;
+    // (+ 0.f: at a masked position pr is +0 and the product -0 whenever its other factor is negative; -0 + 0 is +0 bit for bit)
+    float ds = pr * (dp[o] * m + (dattn ? ldf(dattn + o) : 0.f) - dot) * scale + 0.f;
     stf(dscores + o, ds);
     if (dbdb) {
       int si, sc;
@@ -159,7 +161,7 @@ extern "C" int s2svc_attn_softmax_fwd(int dtype, int B, int H, int T1, int T2, i
 extern "C" int s2svc_attn_softmax_bwd(int dtype, int B, int H, int T1, int T2, int ld, const void* attn, const float* dp, const void* dattn,
                                       float scale, float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* dscores, void* dbd, int Lp,
                                       int ldb, int rel_mode, void* stream) {
-  S2S_REQUIRE(B >= 0 && H > 0 && T1 >= 0 && T2 > 0 && (!dbd || ldb >= Lp), "attn_softmax_bwd: bad shape");
+  S2S_REQUIRE(B >= 0 && H > 0 && T1 >= 0 && T2 > 0 && ld >= T2 && (!dbd || ldb >= Lp), "attn_softmax_bwd: bad shape");
   const int64_t nrows = (int64_t)B * H * T1;
   if (nrows == 0) return 0;
   hipStream_t st = (hipStream_t)stream;

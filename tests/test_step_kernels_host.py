@@ -323,9 +323,6 @@ LEDGER = {
     "s2svc_add_head_bias_ld": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
     "s2svc_add_rows": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
     "s2svc_gemm_grouped_batched": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_relattn_fwd": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_attn_fused_fwd": ("case", "gpu_kernel_check", "attention_fused_vs_reference"),
-    "s2svc_attn_fused_bwd": ("case", "gpu_kernel_check", "attention_fused_vs_reference"),
     "s2svc_bn_stats_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_bn_act_apply_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_bn_act_bwd_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
@@ -458,3 +455,8 @@ def test_every_launcher_has_a_kernel_level_check():
                 "s2svc_weighted_sum", "s2svc_weighted_sum_bwd", "s2svc_scalars_axpy", "s2svc_pad_cols", "s2svc_decoder_input", "s2svc_append_eos",
                 "s2svc_copy_rows", "s2svc_stop_labels", "s2svc_add_n", "s2svc_fill_zero", "s2svc_seed_advance"):
         assert re.search(r"\b%s\(" % sym, step[0]) or any(_called_in(step, w) for w in wrappers[sym]), f"{sym} is no longer called by tests/gpu_step_kernel_check.py"
+    # ... and the attention launchers in tests/gpu_attn_kernel_check.py
+    attn = mods["gpu_attn_kernel_check"]
+    for sym in ("s2svc_attn_fused_supported", "s2svc_attn_fused_fwd", "s2svc_attn_fused_bwd", "s2svc_attn_map_supported", "s2svc_attn_map_product_supported",
+                "s2svc_attn_map_fwd", "s2svc_attn_map_bwd", "s2svc_relattn_supported", "s2svc_relattn_fwd", "s2svc_attn_softmax_fwd", "s2svc_attn_softmax_bwd"):
+        assert re.search(r"\b%s\(" % sym, attn[0]) or any(_called_in(attn, w) for w in wrappers[sym]), f"{sym} is no longer called by tests/gpu_attn_kernel_check.py"
