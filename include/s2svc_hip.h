@@ -336,6 +336,27 @@ typedef struct s2svc_gather3_job {
   int32_t out_dtype;
 } s2svc_gather3_job;
 int s2svc_gather3_grouped(const s2svc_gather3_job* jobs /* host */, int n, void* stream);
+/* Every derived copy of the weights in ONE launch (up to 48 jobs; one more launch per further 48), what the optimiser runs
+   after each update: the gathers above (kind GATHER3, fields as in s2svc_gather3_job) and the class matrices of the stride-2
+   transposed convolution (kind TCONV2D: in = fp32 weight (O, C, 3, 3), out = bf16, 9*C*O elements in the layout of
+   s2svc_tconv2d_weights, n0 = O, n1 = C; strides, off and n2 unused).  The work of all jobs is cut into units (an LDS tile
+   or a 4096-element slice) that are spread evenly over the grid; a job whose source and output both have a unit-stride
+   direction is read and written in contiguous runs through LDS.  A copy plus at most one fp32 -> bf16 rounding: the results
+   are those of s2svc_gather3 / s2svc_tconv2d_weights bit for bit.  `jobs` is a HOST array.
+   _plan (host only, no device needed): the path (0 element-wise, 1 tile, 2 slab, 3 class-matrix tile) and the number of
+   units of every job, as the launch would take them. */
+enum { S2SVC_DERIVED_GATHER3 = 0, S2SVC_DERIVED_TCONV2D = 1 };
+typedef struct s2svc_derived_job {
+  const void* in;      /* fp32 */
+  void* out;
+  int64_t s0, s1, s2, off;
+  int32_t n0, n1, n2;
+  int32_t out_dtype;
+  int32_t kind;        /* S2SVC_DERIVED_* */
+  int32_t reserved_;
+} s2svc_derived_job;
+int s2svc_derived_refresh(const s2svc_derived_job* jobs /* host */, int n, void* stream);
+int s2svc_derived_refresh_plan(const s2svc_derived_job* jobs /* host */, int n, int32_t* path /* host, n */, int32_t* units /* host, n */);
 /* dst[o][b][a] (+)= src[o][a][b], fp32, o < n: a convolution weight gradient (C_out, taps, C_in) as the GEMM leaves it into the
    parameter's (C_out, C_in, taps) layout (replaces the transposes autograd does inside conv backward: subsampling.py:58-63,
    pre_postnets.py:108-165, alignments.py:28-60 call sites).  A * (B + 1) * 4 bytes must fit 64 KB. */

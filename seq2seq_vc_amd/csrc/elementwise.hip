@@ -355,6 +355,153 @@ __global__ void gather3_grouped_kernel(const gather_jobs g) {
   }
 }
 
+// ---- every derived weight copy in ONE launch (s2svc_derived_refresh) --------------------------------------------------------
+// The host classifies each job once (derived_plan) and lays the jobs' work units -- one LDS tile or one 4096-element slice each --
+// end to end in a flat list; workgroup b takes units b, b + gridDim.x, ...  (gather3_grouped_kernel above spends grid.y on the
+// jobs: every job gets the grid of the largest one, and the small jobs' workgroups exit at once.)
+//   TILE   64 source rows x 64 output columns through a padded LDS tile: read with the lanes along the rows (the (i0, i1) pairs, in
+//          the order that makes consecutive rows consecutive addresses), written with the lanes along i2.  The column gathers of
+//          gather3_grouped_kernel, and with i0 as the fast row index the (taps, C_in, C_out) copy of the Linear behind the Conv2d
+//          front-end, whose rows (f, c) sit at c * taps + f.
+//   TCONV  the same tile over w (O, C*9) -> the four class matrices [c][tap * O + o] of the transposed convolution: row q = c * 9 +
+//          kh * 3 + kw is one output row of its class (s2svc_tconv2d_weights' layout).
+//   SLAB   s1 == 1 and a short s2 (a weight (O, C, k) as (O, k, C): s2 = k): the source of one i0 and `ch` columns is ONE run of
+//          (ch - 1) * s2 + n1 floats; it is read as it lies and written row by row from LDS.  ch = the largest power of two (64 ...
+//          1024) whose run fits the LDS tile, no larger than n2 needs: a unit moves 2-4 K elements between its two barriers.
+//   ELEMENT  the loop of gather3_kernel, for what fits none of these.
+#define S2S_DERIVED_MAX 48
+#define S2S_DERIVED_LDS (64 * 65)
+enum { DR_ELEMENT = 0, DR_TILE = 1, DR_SLAB = 2, DR_TCONV = 3 };
+struct derived_dev_job {
+  const float* in;
+  void* out;
+  int64_t s0, s1, s2, off;
+  int32_t n0, n1, n2;
+  uint8_t path, out_dtype, i0_fast, ch_log2;   // i0_fast: TILE rows run with i0 fastest; ch_log2: SLAB columns per unit (6 ... 10)
+};
+struct derived_jobs {
+  derived_dev_job j[S2S_DERIVED_MAX];
+  int32_t ubeg[S2S_DERIVED_MAX + 1];           // first unit of every job; ubeg[n] = units of the launch
+  int32_t n;
+};
+static_assert(sizeof(derived_jobs) <= 3840, "kernel arguments are limited to 4 KB (the runtime appends its own)");
+
+__device__ __forceinline__ void derived_store(void* out, int out_dtype, int64_t o, float v) {
+  if (out_dtype == S2S_F32) ((float*)out)[o] = v;
+  else ((bf16_t*)out)[o] = f2bf(v);
+}
+
+// source offset and first output element of tile row q (TILE / TCONV)
+__device__ __forceinline__ void derived_row(const derived_dev_job& jb, int q, int64_t& src, int64_t& dst) {
+  if (jb.path == DR_TCONV) {
+    const int O = jb.n0, C = jb.n1;
+    const int c = q / 9, k = q - c * 9, kh = k / 3, kw = k - kh * 3;
+    const int pt = kh & 1, pf = kw & 1, nf = 2 - pf, ntaps = (2 - pt) * nf, tap = (kh >> 1) * nf + (kw >> 1);
+    const int first = pt ? (pf ? 8 : 6) : (pf ? 4 : 0);              // class offsets 0, 4, 6, 8 (x C * O)
+    src = q;
+    dst = (int64_t)first * C * O + ((int64_t)c * ntaps + tap) * O;
+    return;
+  }
+  int i0, i1;
+  if (jb.i0_fast) { i1 = q / jb.n0; i0 = q - i1 * jb.n0; }
+  else { i0 = q / jb.n1; i1 = q - i0 * jb.n1; }
+  src = jb.off + i0 * jb.s0 + i1 * jb.s1;
+  dst = ((int64_t)i0 * jb.n1 + i1) * jb.n2;
+}
+
+__global__ __launch_bounds__(256) void derived_refresh_kernel(const derived_jobs g) {
+  __shared__ float lds[S2S_DERIVED_LDS];
+  __shared__ int64_t row_dst[64];
+  const int total = g.ubeg[g.n];
+  int ji = 0;
+  for (int u = blockIdx.x; u < total; u += gridDim.x) {        // (u, and everything derived from it alone, is uniform)
+    while (g.ubeg[ji + 1] <= u) ++ji;                          // (u < total = ubeg[n]: stops at a job that has units)
+    const derived_dev_job& jb = g.j[ji];
+    const int t = u - g.ubeg[ji];
+    const float* in = jb.in;
+    if (jb.path == DR_TILE || jb.path == DR_TCONV) {
+      const bool tconv = jb.path == DR_TCONV;
+      const int R = tconv ? 9 * jb.n1 : jb.n0 * jb.n1, NC = tconv ? jb.n0 : jb.n2;
+      const int64_t cs = tconv ? (int64_t)9 * jb.n1 : jb.s2;
+      const int tc = (NC + 63) / 64;
+      const int r0 = (t / tc) * 64, c0 = (t - (t / tc) * tc) * 64;
+      const int x = threadIdx.x & 63, y = threadIdx.x >> 6;
+      int64_t src = 0, dst = 0;
+      if (r0 + x < R) derived_row(jb, r0 + x, src, dst);
+      if (y == 0) row_dst[x] = dst;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {                             // (16 independent loads in flight per thread)
+        const int cc = y + 4 * k;
+        lds[cc * 65 + x] = (r0 + x < R && c0 + cc < NC) ? in[src + (int64_t)(c0 + cc) * cs] : 0.f;
+      }
+      __syncthreads();
+      const int c = c0 + x;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        const int rr = y + 4 * k;
+        if (r0 + rr < R && c < NC) derived_store(jb.out, jb.out_dtype, row_dst[rr] + c, lds[x * 65 + rr]);
+      }
+      __syncthreads();
+    } else if (jb.path == DR_SLAB) {
+      const int ch = 1 << jb.ch_log2, tc = (jb.n2 + ch - 1) >> jb.ch_log2;
+      const int i0 = t / tc, c0 = (t - i0 * tc) << jb.ch_log2;
+      const int cols = jb.n2 - c0 < ch ? jb.n2 - c0 : ch;
+      const int s2 = (int)jb.s2, span = (cols - 1) * s2 + jb.n1;
+      const int64_t base = jb.off + i0 * jb.s0 + (int64_t)c0 * s2;
+#pragma unroll 4
+      for (int i = threadIdx.x; i < span; i += 256) lds[i] = in[base + i];
+      __syncthreads();
+      const int64_t o0 = (int64_t)i0 * jb.n1 * jb.n2 + c0;
+      for (int i = threadIdx.x; i < jb.n1 * ch; i += 256) {
+        const int i1 = i >> jb.ch_log2, i2 = i & (ch - 1);
+        if (i2 < cols) derived_store(jb.out, jb.out_dtype, o0 + (int64_t)i1 * jb.n2 + i2, lds[i2 * s2 + i1]);
+      }
+      __syncthreads();
+    } else {
+      const int64_t n = (int64_t)jb.n0 * jb.n1 * jb.n2, e0 = (int64_t)t * 4096;
+      for (int k = 0; k < 16; ++k) {
+        const int64_t i = e0 + k * 256 + threadIdx.x;
+        if (i >= n) break;
+        const int i2 = (int)(i % jb.n2);
+        const int64_t r = i / jb.n2;
+        const int i1 = (int)(r % jb.n1), i0 = (int)(r / jb.n1);
+        derived_store(jb.out, jb.out_dtype, i, in[jb.off + i0 * jb.s0 + i1 * jb.s1 + i2 * jb.s2]);
+      }
+    }
+  }
+}
+
+// The path of one job and how many units it takes (host).  Returns false for a job that is not valid.
+bool derived_plan(const s2svc_derived_job& a, derived_dev_job& d, int64_t& units) {
+  if (!a.in || !a.out || a.n0 <= 0 || a.n1 <= 0 || (a.out_dtype != S2S_F32 && a.out_dtype != S2S_BF16)) return false;
+  d.in = (const float*)a.in; d.out = a.out;
+  d.s0 = a.s0; d.s1 = a.s1; d.s2 = a.s2; d.off = a.off;
+  d.n0 = a.n0; d.n1 = a.n1; d.n2 = a.n2;
+  d.out_dtype = (uint8_t)a.out_dtype; d.i0_fast = 0; d.ch_log2 = 0;
+  if (a.kind == S2SVC_DERIVED_TCONV2D) {                      // n0 = O, n1 = C
+    if (a.out_dtype != S2S_BF16 || (int64_t)9 * a.n0 * a.n1 >= (int64_t)1 << 31) return false;
+    d.path = DR_TCONV;
+    units = (int64_t)((9 * a.n1 + 63) / 64) * ((a.n0 + 63) / 64);
+    return true;
+  }
+  if (a.kind != S2SVC_DERIVED_GATHER3 || a.n2 <= 0 || (int64_t)a.n0 * a.n1 >= (int64_t)1 << 31) return false;
+  const int64_t a0 = a.s0 < 0 ? -a.s0 : a.s0, a1 = a.s1 < 0 ? -a.s1 : a.s1;
+  if (a.s1 == 1 && a.s2 >= 1 && 63 * a.s2 + a.n1 <= S2S_DERIVED_LDS) {
+    d.path = DR_SLAB;
+    d.ch_log2 = 6;
+    while (d.ch_log2 < 10 && (1 << d.ch_log2) < a.n2 && ((2 << d.ch_log2) - 1) * a.s2 + a.n1 <= S2S_DERIVED_LDS) ++d.ch_log2;
+    units = (int64_t)a.n0 * ((a.n2 + (1 << d.ch_log2) - 1) >> d.ch_log2);
+  } else if (a.n2 >= 32 && a.s2 >= 64 && ((a.s2 > a0 && a.s2 > a1) || a0 == 1 || a1 == 1)) {
+    d.path = DR_TILE;
+    d.i0_fast = a1 != 1 && a0 == 1;
+    units = (((int64_t)a.n0 * a.n1 + 63) / 64) * ((a.n2 + 63) / 64);
+  } else {
+    d.path = DR_ELEMENT;
+    units = ((int64_t)a.n0 * a.n1 * a.n2 + 4095) / 4096;
+  }
+  return true;
+}
+
 template <typename T>
 int launch_typed1(int dtype);
 
@@ -564,6 +711,39 @@ extern "C" int s2svc_gather3_grouped(const s2svc_gather3_job* jobs, int n, void*
     if (bx > 2048) bx = 2048;
     hipLaunchKernelGGL(gather3_grouped_kernel, dim3(bx, g.n), dim3(256), 0, st, g);
     S2S_CHECK_LAUNCH("gather3_grouped_kernel");
+  }
+  return 0;
+}
+
+extern "C" int s2svc_derived_refresh_plan(const s2svc_derived_job* jobs, int n, int32_t* path, int32_t* units) {
+  S2S_REQUIRE(n >= 0 && (n == 0 || (jobs && path && units)), "derived_refresh_plan: bad args");
+  for (int i = 0; i < n; ++i) {
+    derived_dev_job d;
+    int64_t u = 0;
+    S2S_REQUIRE(derived_plan(jobs[i], d, u) && u < ((int64_t)1 << 31), "derived_refresh_plan: bad job");
+    path[i] = d.path;
+    units[i] = (int32_t)u;
+  }
+  return 0;
+}
+
+extern "C" int s2svc_derived_refresh(const s2svc_derived_job* jobs, int n, void* stream) {
+  S2S_REQUIRE(n >= 0 && (n == 0 || jobs), "derived_refresh: bad args");
+  for (int i0 = 0; i0 < n; i0 += S2S_DERIVED_MAX) {              // (one launch; a second one only past S2S_DERIVED_MAX jobs)
+    derived_jobs g = {};
+    g.n = (n - i0 < S2S_DERIVED_MAX) ? n - i0 : S2S_DERIVED_MAX;
+    int64_t total = 0;
+    for (int i = 0; i < g.n; ++i) {
+      int64_t u = 0;
+      S2S_REQUIRE(derived_plan(jobs[i0 + i], g.j[i], u), "derived_refresh: bad job");
+      g.ubeg[i] = (int32_t)total;
+      total += u;
+      S2S_REQUIRE(total < ((int64_t)1 << 31), "derived_refresh: too many work units");
+    }
+    for (int i = g.n; i <= S2S_DERIVED_MAX; ++i) g.ubeg[i] = (int32_t)total;
+    const int bx = total < 2048 ? (int)total : 2048;
+    hipLaunchKernelGGL(derived_refresh_kernel, dim3(bx), dim3(256), 0, (hipStream_t)stream, g);
+    S2S_CHECK_LAUNCH("derived_refresh_kernel");
   }
   return 0;
 }

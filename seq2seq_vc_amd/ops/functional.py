@@ -1494,7 +1494,7 @@ class _Conv2dS2(Function):
         if ctx.needs_input_grad[0] and dtype == torch.bfloat16 and O % 8 == 0 and O >= 64 and C % 8 == 0:
             # transposed convolution as four implicit GEMMs, one per parity class (t1 % 2, f1 % 2) of input pixels: each
             # gathers its 4 / 2 / 2 / 1 taps of dY straight from HBM and stores into its pixels of dX (no dcols, no col2im)
-            wts = K.tconv2d_weights(weight.detach())
+            wts = K.tconv2d_weights_cached(weight)       # a managed weight: kept fresh by the optimiser, nothing launched here
             dx = torch.empty((B, T1, F1, C), dtype=dtype, device=x.device)
             mask = x if ctx.input_is_relu else None     # x = relu(u): the GEMMs hand back dL/du (mask rows follow the c_map)
             for cls, wt in enumerate(wts):

@@ -944,13 +944,20 @@ class PermRegistry(list):
     """The permuted weight copies one optimiser (optim.FlatAdam) keeps fresh: (weight, key, buffer) jobs, appended by
     gather3_cached in order of first use.  FlatAdam.step() and refresh_shadow() recompute all of them in line, on the stream
     they run on (FlatAdam.refresh_derived).  `covered` = how many of them the CAPTURED refresh launch updates on replay
-    (None: the refresh runs from Python and updates all of them)."""
+    (None: the refresh runs from Python and updates all of them).
+    `tconv` / `tconv_covered`: the same for the class matrices of the stride-2 transposed convolution, (weight, buffer) jobs
+    appended by tconv2d_weights_cached (their four tap sets are no 3-index gather, so they are no entries of the list itself)."""
     covered = None
+    tconv_covered = None
+
+    def __init__(self, *args):
+        super().__init__(*args)
+        self.tconv = []
 
 
 def gather3_cached(weight, n, strides, off, out_dtype):
     """gather3 of a PARAMETER.  When optim.FlatAdam manages it, the permuted copy lives in a persistent buffer that the
-    optimiser refreshes in line after every update -- ONE grouped launch for all such copies of the model (gather3_refresh)
+    optimiser refreshes in line after every update -- ONE launch for all such copies of the model (derived_refresh)
     instead of a launch per convolution and pass on the step's dependency chain; otherwise a plain gather3 of the current
     values.  A captured refresh updates only the copies registered at capture time (`covered`): a copy registered later, or
     whose weight torch changed in place since (`_version`), is gathered again here, on use."""
@@ -981,6 +988,44 @@ def gather3_refresh(registry):
         jb.s0, jb.s1, jb.s2, jb.off = st[0], st[1], st[2], off
         jb.n0, jb.n1, jb.n2, jb.out_dtype = n[0], n[1], n[2], _DT[odt]
     _lib.check(_lib.lib().s2svc_gather3_grouped(ctypes.addressof(jobs), len(registry), stream()), "gather3_grouped")
+
+
+def derived_jobs(gathers, tconvs=()):
+    """The job array of s2svc_derived_refresh: gathers = (fp32 source, (n, strides, off, out dtype), buffer) as PermRegistry
+    holds them, tconvs = (fp32 weight (O, C, 3, 3), bf16 buffer of 9 * C * O elements)."""
+    jobs = (_lib.DerivedJob * (len(gathers) + len(tconvs)))()
+    for jb, (w, (n, st, off, odt), buf) in zip(jobs, gathers):
+        jb.in_, jb.out, jb.kind = w.data_ptr(), buf.data_ptr(), 0
+        jb.s0, jb.s1, jb.s2, jb.off = st[0], st[1], st[2], off
+        jb.n0, jb.n1, jb.n2, jb.out_dtype = n[0], n[1], n[2], _DT[odt]
+    for i, (w, buf) in enumerate(tconvs):
+        jb = jobs[len(gathers) + i]
+        jb.in_, jb.out, jb.kind = w.data_ptr(), buf.data_ptr(), 1
+        jb.n0, jb.n1, jb.n2, jb.out_dtype = w.shape[0], w.shape[1], 1, _DT[torch.bfloat16]
+    return jobs
+
+
+def derived_refresh(gathers, tconvs=()):
+    """Recompute every derived copy from the current fp32 weights in ONE launch: the permuted copies (what gather3 returns) and
+    the class matrices of the transposed convolution (what tconv2d_weights returns), bit for bit."""
+    if not gathers and not tconvs:
+        return
+    for w, buf in tconvs:
+        if w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or \
+                buf.dtype != torch.bfloat16 or buf.numel() != w.numel() or not buf.is_contiguous():
+            raise ValueError("derived_refresh: a class-matrix job takes a contiguous fp32 (O, C, 3, 3) weight and a bf16 buffer of its size")
+    jobs = derived_jobs(gathers, tconvs)
+    _lib.check(_lib.lib().s2svc_derived_refresh(ctypes.addressof(jobs), len(jobs), stream()), "derived_refresh")
+
+
+def derived_refresh_plan(gathers, tconvs=()):
+    """[(path, units)] per job as s2svc_derived_refresh would run them (host arithmetic of the library, no device needed):
+    path 0 element-wise, 1 tile, 2 slab, 3 class-matrix tile."""
+    jobs = derived_jobs(gathers, tconvs)
+    path, units = (ctypes.c_int32 * len(jobs))(), (ctypes.c_int32 * len(jobs))()
+    _lib.check(_lib.lib().s2svc_derived_refresh_plan(ctypes.addressof(jobs), len(jobs), ctypes.addressof(path), ctypes.addressof(units)),
+               "derived_refresh_plan")
+    return list(zip(path, units))
 
 
 def gather3(x, n, strides, off, out_dtype):
@@ -1101,11 +1146,38 @@ def tconv2d_weights(weight):
     O, C = weight.shape[0], weight.shape[1]
     out = torch.empty(9 * C * O, dtype=torch.bfloat16, device=weight.device)
     _lib.check(_lib.lib().s2svc_tconv2d_weights(O, C, ptr(weight), ptr(out), stream()), "tconv2d_weights")
+    return _tconv2d_views(out, O, C)
+
+
+def _tconv2d_views(out, O, C):
     views, off = [], 0
     for ntaps in (4, 2, 2, 1):
         views.append(out[off:off + C * ntaps * O].view(C, ntaps * O))
         off += C * ntaps * O
     return views
+
+
+def tconv2d_weights_cached(weight):
+    """tconv2d_weights of a PARAMETER.  When optim.FlatAdam manages it, the class matrices live in a persistent buffer that the
+    optimiser's refresh launch rewrites after every update (derived_refresh), so the backward pass launches nothing for them;
+    otherwise they are computed here, on use.  The staleness rules are those of gather3_cached: a copy registered after a captured
+    refresh (`tconv_covered`), or whose weight torch changed in place since (`_version`), is computed again on use."""
+    reg = getattr(weight, "_s2s_perm_registry", None)
+    if reg is None or not hasattr(weight, "_s2s_perms"):
+        return tconv2d_weights(weight.detach())
+    O, C = weight.shape[0], weight.shape[1]
+    ent = weight._s2s_perms.get("tconv2d")
+    if ent is None:
+        buf = torch.empty(9 * C * O, dtype=torch.bfloat16, device=weight.device)
+        _lib.check(_lib.lib().s2svc_tconv2d_weights(O, C, ptr(weight), ptr(buf), stream()), "tconv2d_weights")
+        views = _tconv2d_views(buf, O, C)
+        weight._s2s_perms["tconv2d"] = [buf, weight._version, len(reg.tconv), views]
+        reg.tconv.append((weight, buf))
+        return views
+    if ent[1] != weight._version or (reg.tconv_covered is not None and ent[2] >= reg.tconv_covered):
+        _lib.check(_lib.lib().s2svc_tconv2d_weights(O, C, ptr(weight), ptr(ent[0]), stream()), "tconv2d_weights")
+        ent[1] = weight._version
+    return ent[3]
 
 
 def col2im_s2(dcols, B, T1, F1, C, T2, F2):

@@ -235,21 +235,24 @@ class FlatAdam:
     def refresh_derived(self):
         """Every derived copy of the weights, in line on the current stream -- called from exactly step() and refresh_shadow(), so
         nothing that reads a copy can see a stale one: the permuted convolution weights that the forward / backward passes
-        registered (ops.kernels.gather3_cached; one grouped launch), then the transposed bf16 shadow (one tile-transpose launch).
-        Copies that a captured refresh cannot know (`covered`) are gathered again on use."""
+        registered (ops.kernels.gather3_cached) and the class matrices of the front-end's transposed convolution
+        (tconv2d_weights_cached) in ONE launch, then the transposed bf16 shadow (one tile-transpose launch).
+        Copies that a captured refresh cannot know (`covered`, `tconv_covered`) are computed again on use."""
         reg = self._perm_jobs
-        K.gather3_refresh(reg)
+        K.derived_refresh(reg, reg.tconv)
         if self.flat_p.is_cuda and torch.cuda.is_current_stream_capturing():
             # a captured refresh updates exactly the copies registered NOW on every replay; copies that register later (first
             # evaluation in another dtype, a convolution first used later) are not in it
             reg.covered = len(reg) if reg.covered is None else min(reg.covered, len(reg))
+            reg.tconv_covered = len(reg.tconv) if reg.tconv_covered is None else min(reg.tconv_covered, len(reg.tconv))
         if self.shadow_t is not None:
             K.transpose_tiles(self.t_tiles, self.shadow, self.shadow_t)
 
     # After an optimiser step three memory-bound passes stand between it and the next backward pass: the permuted convolution
-    # weights (needed by the forward pass), the transposed bf16 shadow (data-gradient GEMMs) and the zero-fill of the flat
-    # gradient buffer (weight-gradient kernels accumulate): 136 + 144 + 80 us of a 13 ms AAS-VC step, 32 + 27 + 18 us of a
-    # 4.0 ms VTN step.  They run IN LINE: the refresh at the end of step(), the zero-fill in begin_step() / zero_grad().
+    # weights with the class matrices of the front-end's transposed convolution (needed by the forward / backward pass; ONE
+    # launch, ops.kernels.derived_refresh), the transposed bf16 shadow (data-gradient GEMMs) and the zero-fill of the flat
+    # gradient buffer (weight-gradient kernels accumulate): 82 + 145 + 80 us of a 10.9 ms AAS-VC step, 24 + 31 + 17 us of a
+    # 3.6 ms VTN step.  They run IN LINE: the refresh at the end of step(), the zero-fill in begin_step() / zero_grad().
     # (Running them on a stream of their own beside the forward pass lost: 13.0 vs 12.74 ms per AAS-VC step, VTN equal; as capped
     # grids of 16 ... 2048 workgroups 11.52-11.59 vs 11.40 ms -- what runs beside the forward chain is not free even when it is
     # HBM-bound.  profiles/AB_LOG.md.)
