@@ -133,6 +133,12 @@ typedef struct {
 } s2svc_gemm_desc;
 
 int s2svc_gemm(const s2svc_gemm_desc* desc /* host */, void* stream);
+/* Which kernel ran (tests): the name of the kernel instantiation that the most recent s2svc_gemm call of the calling thread launched,
+   with the template arguments that tell the variants apart -- "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5,lean>", "glds_k2<32,64,3>",
+   "8ph_q<CONV1D,2,4>", "fast<f32,32,32,128,KC,KC>", "generic<bf16,64,64>", "skinny<bf16,1,lean>" -- followed by "+splitk_reduce" and /
+   or "+stage_pass" when the call added those launches; "" when it launched nothing.  The name is set where the kernel is launched.  The
+   string belongs to the library and holds until the thread's next call of this function. */
+const char* s2svc_gemm_last_route(void);
 
 /* Weight matrices of the four parity classes of the 3x3 stride-2 transposed convolution (S2SVC_OP_TCONV2D_S2), from the
    fp32 master weight w (O, C, 3, 3): out (bf16) = class (0,0) | (0,1) | (1,0) | (1,1), class (pt, pf) = [C][ntaps*O] with

@@ -313,7 +313,7 @@ _lib = None
 
 def exported_symbols():
     """Every symbol include/s2svc_hip.h declares (checked by the CPU-side ABI test)."""
-    return sorted(list(_SIGS) + list(_RET64) + ["s2svc_last_error", "s2svc_abi_version"])
+    return sorted(list(_SIGS) + list(_RET64) + ["s2svc_last_error", "s2svc_abi_version", "s2svc_gemm_last_route"])
 
 
 def lib():
@@ -340,6 +340,7 @@ def lib():
         fn.restype = ctypes.c_int64
     L.s2svc_last_error.restype = ctypes.c_char_p
     L.s2svc_abi_version.restype = ctypes.c_int
+    L.s2svc_gemm_last_route.restype = ctypes.c_char_p
     _lib = L
     return L
 

@@ -303,6 +303,7 @@ int launch_stage_pass(const s2svc_gemm_desc& d, hipStream_t st) {
   const int64_t total = (int64_t)d.M * d.N;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;
+  s2s_gemm_route_add("+stage_pass");
   hipLaunchKernelGGL(gemm_stage_kernel, dim3(blocks), dim3(256), 0, st, d);
   S2S_CHECK_LAUNCH("gemm_stage_kernel");
   return 0;
@@ -312,12 +313,16 @@ template <typename T, int BM, int BN>
 int launch(const s2svc_gemm_desc& d, hipStream_t st) {
   const int splitk = d.splitk > 1 ? d.splitk : 1;
   dim3 grid((d.N + BN - 1) / BN, (d.M + BM - 1) / BM, d.nb0 * d.nb1 * splitk);
+  static_assert(BM == BN && (BM == 64 || BM == 128), "the route names below list the instantiations");
+  s2s_gemm_route(sizeof(T) == 4 ? (BM == 128 ? "generic<f32,128,128>" : "generic<f32,64,64>")
+                                : (BM == 128 ? "generic<bf16,128,128>" : "generic<bf16,64,64>"));
   hipLaunchKernelGGL((gemm_kernel<T, BM, BN>), grid, dim3(256), 0, st, d);
   S2S_CHECK_LAUNCH("gemm_kernel");
   if (splitk > 1) {
     const int64_t total = (int64_t)d.nb0 * d.nb1 * d.M * d.N;
     int blocks = (int)((total + 255) / 256);
     if (blocks > 4096) blocks = 4096;
+    s2s_gemm_route_add("+splitk_reduce");
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, d);
     S2S_CHECK_LAUNCH("splitk_reduce_kernel");
   }
@@ -331,6 +336,18 @@ extern "C" int s2svc_gemm_try_skinny(const s2svc_gemm_desc* desc, void* stream);
 extern "C" int s2svc_gemm_try_glds(const s2svc_gemm_desc* desc, void* stream);    // gemm_glds.hip (bf16, LDS-DMA)
 extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream);     // gemm_8ph.hip (bf16, 256-row tiles, 8 waves)
 
+// the kernel the latest s2svc_gemm call of this thread launched, as its launch site named it (s2svc_gemm_last_route)
+static thread_local const char* g_route = "";
+static thread_local const char* g_route_more[2] = {"", ""};
+void s2s_gemm_route(const char* name) { g_route = name; }
+void s2s_gemm_route_add(const char* suffix) { g_route_more[g_route_more[0][0] ? 1 : 0] = suffix; }
+
+extern "C" const char* s2svc_gemm_last_route(void) {
+  static thread_local char out[160];
+  snprintf(out, sizeof(out), "%s%s%s", g_route, g_route_more[0], g_route_more[1]);
+  return out;
+}
+
 static bool generic_forced() {
   static int v = -1;
   if (v < 0) v = 0;
@@ -340,6 +357,7 @@ static bool generic_forced() {
 extern "C" int s2svc_gemm(const s2svc_gemm_desc* desc, void* stream) {
   S2S_REQUIRE(desc != nullptr, "s2svc_gemm: null desc");
   s2svc_gemm_desc d = *desc;
+  g_route = g_route_more[0] = g_route_more[1] = "";
   if (d.nb0 < 1) d.nb0 = 1;
   if (d.nb1 < 1) d.nb1 = 1;
   S2S_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, "s2svc_gemm: negative dims");
@@ -389,6 +407,7 @@ extern "C" int s2svc_gemm(const s2svc_gemm_desc* desc, void* stream) {
         const int64_t total = (int64_t)d.nb0 * d.nb1 * d.M * d.N;
         int blocks = (int)((total + 255) / 256);
         if (blocks > 4096) blocks = 4096;
+        s2s_gemm_route_add("+splitk_reduce");
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, d);
         S2S_CHECK_LAUNCH("splitk_reduce_kernel");
       }

@@ -1463,10 +1463,12 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
     const int64_t t128 = (int64_t)(d.M / 256) * (d.N / 128);
     if (p8_tr_take_q(d.N % 256 == 0, t128 / 2, t128)) {
       dim3 grid((unsigned)(d.N / 256), (unsigned)(d.M / 256), 1);
+      s2s_gemm_route(mode == 2 ? "8ph_tr_q<noskew>" : "8ph_tr_q<skew>");
       if (mode == 2) hipLaunchKernelGGL((gemm_8ph_tr_kernel_q<false>), grid, dim3(512), 0, (hipStream_t)stream, d);
       else hipLaunchKernelGGL((gemm_8ph_tr_kernel_q<true>), grid, dim3(512), 0, (hipStream_t)stream, d);
     } else {
       dim3 grid((unsigned)(d.N / 128), (unsigned)(d.M / 256), 1);
+      s2s_gemm_route(mode == 2 ? "8ph_tr<noskew>" : "8ph_tr<skew>");
       if (mode == 2) hipLaunchKernelGGL((gemm_8ph_tr_kernel<false>), grid, dim3(512), 0, (hipStream_t)stream, d);
       else hipLaunchKernelGGL((gemm_8ph_tr_kernel<true>), grid, dim3(512), 0, (hipStream_t)stream, d);
     }
@@ -1500,6 +1502,7 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
     const int ph = p8_n96_phases(d, geo, geo == 1 ? t256 : geo == 2 ? t512 : t128);
     if (ph) {
       dim3 grid((unsigned)((d.N + 96 * ph - 1) / (96 * ph)), (unsigned)((d.M + 255) / 256), 1);
+      s2s_gemm_route(ph == 3 ? "8ph_n96<3>" : "8ph_n96<2>");
       if (ph == 3) hipLaunchKernelGGL((gemm_8ph_kernel_n96<3, true>), grid, dim3(512), 0, st, d);
       else hipLaunchKernelGGL((gemm_8ph_kernel_n96<2, true>), grid, dim3(512), 0, st, d);
       S2S_CHECK_LAUNCH("gemm_8ph_kernel_n96");
@@ -1514,6 +1517,7 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
     if (!c1d_on || mode != 1 || nb != 1 || !epilogue_common_ok(d)) return 0;
     const int bm1 = geo == 2 ? 512 : 256, bn1 = geo == 1 ? 256 : 128;
     dim3 grid1((unsigned)((d.N + bn1 - 1) / bn1), (unsigned)((d.M + bm1 - 1) / bm1), 1);
+    s2s_gemm_route(geo == 1 ? "8ph_q<CONV1D,2,4>" : geo == 2 ? "8ph_q<CONV1D,4,2>" : "8ph_128<CONV1D,lean>");
     if (geo == 1) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_CONV1D, 2, 4, true, true>), grid1, dim3(512), 0, st, d);
     else if (geo == 2) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_CONV1D, 4, 2, true, true>), grid1, dim3(512), 0, st, d);
     else hipLaunchKernelGGL((gemm_8ph_kernel_128<P8_CONV1D, true, 1>), grid1, dim3(512), 0, st, d);
@@ -1523,8 +1527,10 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
   const bool conv = d.A.mode == S2SVC_OP_CONV2D_S2, tconv = d.A.mode == S2SVC_OP_TCONV2D_S2;
   const int bm = geo == 2 ? 512 : 256, bn = geo == 1 ? 256 : 128;
   dim3 grid((unsigned)((d.N + bn - 1) / bn), (unsigned)((d.M + bm - 1) / bm), (unsigned)nb);
-#define P8_LAUNCH(KERNEL, ...)                                                                            \
+#define P8_LAUNCH(PRE, POST, KERNEL, ...)                                                                   \
   do {                                                                                                    \
+    s2s_gemm_route(mode == 2 ? (conv ? PRE "CONV2D" POST ",noskew>" : tconv ? PRE "TCONV2D" POST ",noskew>" : PRE "DENSE" POST ",noskew>")    \
+                             : (conv ? PRE "CONV2D" POST ",skew>" : tconv ? PRE "TCONV2D" POST ",skew>" : PRE "DENSE" POST ",skew>"));        \
     if (mode == 2) {                                                                                      \
       if (conv) hipLaunchKernelGGL((KERNEL<P8_CONV2D, ##__VA_ARGS__, false>), grid, dim3(512), 0, st, d); \
       else if (tconv) hipLaunchKernelGGL((KERNEL<P8_TCONV2D, ##__VA_ARGS__, false>), grid, dim3(512), 0, st, d); \
@@ -1537,14 +1543,16 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
   } while (0)
   static const bool lean_on = true;
   if (lean_on && !conv && !tconv && mode != 2 && epilogue_common_ok(d)) {       // dense operands + the common epilogue: lean variants
+    s2s_gemm_route(geo == 1 ? "8ph_q<DENSE,2,4,lean>" : geo == 2 ? "8ph_q<DENSE,4,2,lean>" : "8ph_128<DENSE,lean>");
     if (geo == 1) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_DENSE, 2, 4, true, true>), grid, dim3(512), 0, st, d);
     else if (geo == 2) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_DENSE, 4, 2, true, true>), grid, dim3(512), 0, st, d);
     else hipLaunchKernelGGL((gemm_8ph_kernel_128<P8_DENSE, true, 1>), grid, dim3(512), 0, st, d);
   } else if (lean_on && geo == 3 && !conv && !tconv && mode != 2 && epilogue_swish_ok(d)) {        // the Conformer feed-forward pair
+    s2s_gemm_route("8ph_128<DENSE,swish>");
     hipLaunchKernelGGL((gemm_8ph_kernel_128<P8_DENSE, true, 2>), grid, dim3(512), 0, st, d);
-  } else if (geo == 1) P8_LAUNCH(gemm_8ph_kernel_q, 2, 4);
-  else if (geo == 2) P8_LAUNCH(gemm_8ph_kernel_q, 4, 2);
-  else P8_LAUNCH(gemm_8ph_kernel_128);
+  } else if (geo == 1) P8_LAUNCH("8ph_q<", ",2,4", gemm_8ph_kernel_q, 2, 4);
+  else if (geo == 2) P8_LAUNCH("8ph_q<", ",4,2", gemm_8ph_kernel_q, 4, 2);
+  else P8_LAUNCH("8ph_128<", "", gemm_8ph_kernel_128);
 #undef P8_LAUNCH
   S2S_CHECK_LAUNCH("gemm_8ph_kernel");
   return 1;

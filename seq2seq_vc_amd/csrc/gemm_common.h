@@ -6,6 +6,12 @@
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
+// s2svc_gemm_last_route (include/s2svc_hip.h): every launch site of the GEMM families names the kernel instantiation it launches, right
+// where it launches it (gemm.hip keeps the name per thread).  The names are string literals: tests/test_gemm_kernels_host.py lists them
+// by scanning these sources, so a new launch site needs a new literal and a case that claims it.
+void s2s_gemm_route(const char* name);         // the GEMM kernel of this thread's current s2svc_gemm call
+void s2s_gemm_route_add(const char* suffix);   // a further launch of the same call: "+splitk_reduce", "+stage_pass"
+
 // d swish(x) / dx from the pre-activation (the formula of act_dropout_bwd, elementwise.hip)
 __device__ __forceinline__ float swish_grad(float x) {
   const float sg = 1.f / (1.f + expf(-x));

@@ -317,19 +317,28 @@ template <typename T, int BM, int BN, int BK>
 void launch_modes(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   const bool arc = d.A.layout == S2SVC_LAYOUT_RC, brc = d.B.layout == S2SVC_LAYOUT_RC;
   static const bool lean_on = true;
+  // the instantiations of s2svc_gemm_try_fast, by name (s2svc_gemm_last_route); MODES: the operand layouts and the epilogue
+  static_assert(sizeof(T) == 4 ? ((BM == 128 && BK == 32) || (BM == 64 && BK == 64) || (BM == 32 && BK == 128)) : ((BM == 128 && BK == 64) || (BM == 64 && BK == 128)),
+                "a new instantiation needs a route name");
+#define S2S_FAST_ROUTE(MODES)                                                                                                        \
+  s2s_gemm_route(sizeof(T) == 4 ? (BM == 128 ? "fast<f32,128,128,32," MODES ">" : BM == 64 ? "fast<f32,64,64,64," MODES ">" : "fast<f32,32,32,128," MODES ">") \
+                                : (BM == 128 ? "fast<bf16,128,128,64," MODES ">" : "fast<bf16,64,64,128," MODES ">"))
+#define S2S_FAST_ROUTE_LEAN(MODES) s2s_gemm_route(BM == 64 ? "fast<f32,64,64,64," MODES ",lean>" : "fast<f32,32,32,128," MODES ",lean>")
   if constexpr (sizeof(T) == 4 && BM <= 64) {
     if (lean_on && d.A.mode == S2SVC_OP_DENSE && d.B.mode == S2SVC_OP_DENSE && epilogue_common32_ok(d)) {
-      if (!arc && !brc) hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_KC, true>), grid, dim3(256), 0, st, d);
-      else if (!arc && brc) hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_RC, true>), grid, dim3(256), 0, st, d);
-      else if (arc && !brc) hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_RC, AM_KC, true>), grid, dim3(256), 0, st, d);
-      else hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_RC, AM_RC, true>), grid, dim3(256), 0, st, d);
+      if (!arc && !brc) { S2S_FAST_ROUTE_LEAN("KC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_KC, true>), grid, dim3(256), 0, st, d); }
+      else if (!arc && brc) { S2S_FAST_ROUTE_LEAN("KC,RC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_RC, true>), grid, dim3(256), 0, st, d); }
+      else if (arc && !brc) { S2S_FAST_ROUTE_LEAN("RC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_RC, AM_KC, true>), grid, dim3(256), 0, st, d); }
+      else { S2S_FAST_ROUTE_LEAN("RC,RC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_RC, AM_RC, true>), grid, dim3(256), 0, st, d); }
       return;
     }
   }
-  if (!arc && !brc) hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_KC, AM_KC>), grid, dim3(256), 0, st, d);
-  else if (!arc && brc) hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_KC, AM_RC>), grid, dim3(256), 0, st, d);
-  else if (arc && !brc) hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_RC, AM_KC>), grid, dim3(256), 0, st, d);
-  else hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_RC, AM_RC>), grid, dim3(256), 0, st, d);
+  if (!arc && !brc) { S2S_FAST_ROUTE("KC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_KC, AM_KC>), grid, dim3(256), 0, st, d); }
+  else if (!arc && brc) { S2S_FAST_ROUTE("KC,RC"); hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_KC, AM_RC>), grid, dim3(256), 0, st, d); }
+  else if (arc && !brc) { S2S_FAST_ROUTE("RC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_RC, AM_KC>), grid, dim3(256), 0, st, d); }
+  else { S2S_FAST_ROUTE("RC,RC"); hipLaunchKernelGGL((gemm_fast_kernel<T, BM, BN, BK, AM_RC, AM_RC>), grid, dim3(256), 0, st, d); }
+#undef S2S_FAST_ROUTE
+#undef S2S_FAST_ROUTE_LEAN
 }
 
 bool operand_ok(const s2svc_operand& o, int vec, size_t esz) {

@@ -904,6 +904,7 @@ bool launch_kinds(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   }
 #define S2S_GLDS_CASE(KA, KB)                                                                       \
   if (ka == KA && kb == KB) {                                                                      \
+    s2s_gemm_route(BM == 128 ? "glds<128,128," #KA "," #KB ">" : "glds<64,64," #KA "," #KB ">");     \
     hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, KA, KB>), grid, dim3(256), 0, st, d);              \
     return true;                                                                                   \
   }
@@ -912,10 +913,12 @@ bool launch_kinds(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   // measured ~2x slower; BK = 32 with 3-4 stages measured 10-15 % slower).
 #define S2S_DMA_CASE(KA, KB)                                                                        \
   if (ka == KA && kb == KB && !d.a_rowsum && BM == 64 && dma_stages() != 2) {                      \
+    s2s_gemm_route("glds_dma<64,64," #KA "," #KB ",3>");                                           \
     hipLaunchKernelGGL((gemm_dma_kernel<64, 64, KA, KB, 3, 64>), grid, dim3(256), 0, st, d);       \
     return true;                                                                                   \
   }
   if (ka == G_KC_DENSE && kb == G_KC_DENSE && !d.a_rowsum && BM == 64 && dma_stages() != 2 && lean_enabled() && epilogue_common_ok(d)) {
+    s2s_gemm_route("glds_dma<64,64,G_KC_DENSE,G_KC_DENSE,3,lean>");
     hipLaunchKernelGGL((gemm_dma_kernel<64, 64, G_KC_DENSE, G_KC_DENSE, 3, 64, true>), grid, dim3(256), 0, st, d);
     return true;
   }
@@ -1209,18 +1212,23 @@ extern "C" int s2svc_gemm_try_glds(const s2svc_gemm_desc* desc, void* stream) {
     // its own DMA round trip
     const bool lean = lean_enabled() && epilogue_common_ok(d);
     if (lean && k2_enabled() && splitk == 1 && d.nb0 * d.nb1 == 1 && (d.K + 63) / 64 >= k2_min_tiles()) {
+      s2s_gemm_route("glds_k2<32,64,3>");
       hipLaunchKernelGGL((gemm_dma_k2_kernel<32, 64, 3>), dim3(grid.x, grid.y, 1), dim3(512), 0, st, d);
       S2S_CHECK_LAUNCH("gemm_dma_k2_kernel");
       return 1;
     }
     if (deep_stages() && (d.K + 63) / 64 / splitk >= deep_min_tiles()) {
+      s2s_gemm_route(lean ? "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5,lean>" : "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5>");
       if (lean) hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 5, 64, true>), grid, dim3(256), 0, st, d);
       else hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 5, 64>), grid, dim3(256), 0, st, d);
     }
-    else if (lean)
+    else if (lean) {
+      s2s_gemm_route("glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,3,lean>");
       hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3, 64, true>), grid, dim3(256), 0, st, d);
-    else
+    } else {
+      s2s_gemm_route("glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,3>");
       hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3, 64>), grid, dim3(256), 0, st, d);
+    }
     S2S_CHECK_LAUNCH("gemm_dma_kernel");
     return 1;
   }

@@ -106,14 +106,14 @@ void launch_skinny(const s2svc_gemm_desc& d, hipStream_t st) {
   const int mt = (d.M + 15) / 16;
   static const bool lean_on = true;
   if (lean_on && mt <= 2 && epilogue_lean_ok(d)) {
-    if (mt == 1) hipLaunchKernelGGL((gemm_skinny_kernel<T, 1, true>), grid, block, 0, st, d);
-    else hipLaunchKernelGGL((gemm_skinny_kernel<T, 2, true>), grid, block, 0, st, d);
+    if (mt == 1) { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,1,lean>" : "skinny<bf16,1,lean>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 1, true>), grid, block, 0, st, d); }
+    else { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,2,lean>" : "skinny<bf16,2,lean>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 2, true>), grid, block, 0, st, d); }
     return;
   }
-  if (mt == 1) hipLaunchKernelGGL((gemm_skinny_kernel<T, 1>), grid, block, 0, st, d);
-  else if (mt == 2) hipLaunchKernelGGL((gemm_skinny_kernel<T, 2>), grid, block, 0, st, d);
-  else if (mt == 3) hipLaunchKernelGGL((gemm_skinny_kernel<T, 3>), grid, block, 0, st, d);
-  else hipLaunchKernelGGL((gemm_skinny_kernel<T, 4>), grid, block, 0, st, d);
+  if (mt == 1) { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,1>" : "skinny<bf16,1>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 1>), grid, block, 0, st, d); }
+  else if (mt == 2) { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,2>" : "skinny<bf16,2>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 2>), grid, block, 0, st, d); }
+  else if (mt == 3) { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,3>" : "skinny<bf16,3>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 3>), grid, block, 0, st, d); }
+  else { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,4>" : "skinny<bf16,4>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 4>), grid, block, 0, st, d); }
 }
 
 }  // namespace

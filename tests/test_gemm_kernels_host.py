@@ -1,0 +1,327 @@
+"""CPU tests behind tests/gpu_gemm_kernel_check.py.  The float64 restatement of tests/gemm_kernels_ref.py is pinned to torch (matmul, conv1d,
+conv2d and their autograd, the activations); every exact-regime case is shown to be exact (the 2^24 bound on the actual tensors, and the
+float32 restatement equal to the float64 one bit for bit); the power check shows that each planted error fails the rule the GPU case
+applies, on the very inputs the GPU case uses; every route name a launch site of csrc/gemm*.hip can report is claimed by a case or excused
+with the constexpr switch that makes it unreachable.  None of this touches the package's kernels."""
+import os
+import re
+from types import SimpleNamespace as NS
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import gemm_kernels_ref as G
+import step_kernels_ref as R
+
+F32, F64, BF16 = torch.float32, torch.float64, torch.bfloat16
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KC, RC = G.KC, G.RC
+
+
+def close64(a, b, tol=1e-12):
+    a, b = torch.as_tensor(a, dtype=F64), torch.as_tensor(b, dtype=F64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    assert float((a - b).abs().max()) <= tol * max(1.0, float(b.abs().max())), float((a - b).abs().max())
+
+
+def _prob(A, B, M, N, K, **kw):
+    """A bare problem around two operands: no epilogue unless named."""
+    cb = G._out_buf(kw.get("nb0", 1), kw.get("nb1", 1), kw.pop("c_rows_total", M), N, F64, contiguous=False)
+    p = NS(A=A, B=B, M=M, N=N, K=K, nb0=1, nb1=1, dtype=F32, c_dtype=F32, alpha=1.0, bias=None, act="none", drop_p=0.0, emask=None, emask_mode=0,
+           res=None, accumulate=False, Cbuf=cb, c_pre=None, a_rowsum=None, a_rowsum_accumulate=False, splitk=1, stages=3, c_map=None)
+    p.__dict__.update(kw)
+    return p
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# pins
+# ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("la,lb,mis", [(KC, KC, None), (KC, RC, "A"), (RC, KC, "B"), (RC, RC, "AB")])
+def test_dense_restatement_vs_matmul(la, lb, mis):
+    """ld > extent, a pointer offset, two-level batch strides, zero padding: the product, then every stage of the epilogue in its order."""
+    nb0, nb1, M, N, K = 2, 3, 7, 5, 11
+    a, b = R.randn(nb0, nb1, M, K, seed=1).double(), R.randn(nb0, nb1, N, K, seed=2).double()
+    A, B = G._dense_op(a, la, True, mis in ("A", "AB")), G._dense_op(b, lb, True, mis in ("B", "AB"))
+    assert A.ld > (K if la == KC else M) and A.off > 0 and A.bs0 == nb1 * A.bs1 and bool(torch.isnan(A.buf).any())
+    p = _prob(A, B, M, N, K, nb0=nb0, nb1=nb1)
+    want = torch.matmul(a, b.transpose(-2, -1))
+    close64(G.gemm_ref(p, F64).C, want)
+    bias, res, prev = R.randn(N, seed=3), R.randn(nb0, nb1, M, N, seed=4).double(), R.randn(nb0, nb1, M, N, seed=5).double()
+    p.alpha, p.bias, p.act, p.accumulate = 0.37, bias, "tanh", True
+    p.res = G._out_buf(nb0, nb1, M, N, F64, contiguous=False, fill=G.NAN)
+    p.c_pre = G._out_buf(nb0, nb1, M, N, F64, contiguous=False)
+    G._fill(p.res, res), G._fill(p.Cbuf, prev)
+    r = G.gemm_ref(p, F64)
+    pre = R.f32(0.37) * want + bias.double()
+    close64(r.c_pre, pre), close64(r.C, torch.tanh(pre) + res + prev)
+
+
+def test_dropout_mask_stage_sits_between_activation_and_residual():
+    M, N, K = 6, 8, 9
+    a, b = R.randn(1, 1, M, K, seed=1).double(), R.randn(1, 1, N, K, seed=2).double()
+    p = _prob(G._dense_op(a, KC, False, False), G._dense_op(b, KC, False, False), M, N, K, act="relu", drop_p=0.5)
+    keep = G.host_keep(M, N, 0.5, seed=3)
+    e, res = R.randn(1, 1, M, N, seed=4).double(), R.randn(1, 1, M, N, seed=5).double()
+    p.emask, p.res = G._out_buf(1, 1, M, N, F64, contiguous=True, fill=G.NAN), G._out_buf(1, 1, M, N, F64, contiguous=False, fill=G.NAN)
+    G._fill(p.emask, e), G._fill(p.res, res)
+    v = torch.relu(torch.matmul(a, b.transpose(-2, -1))) * keep.double()
+    close64(G.gemm_ref(p, F64, keep).C, torch.where(e > 0, v, torch.zeros((), dtype=F64)) + res)
+    p.emask_mode = 1
+    x = e.clone().requires_grad_(True)
+    F.silu(x).sum().backward()
+    close64(G.gemm_ref(p, F64, keep).C, v * x.grad + res)
+
+
+def test_activations_vs_torch():
+    x = torch.linspace(-6, 6, 97, dtype=F64)
+    for name, fn in (("none", lambda t: t), ("relu", F.relu), ("tanh", torch.tanh), ("swish", F.silu), ("sigmoid", torch.sigmoid), ("gelu", F.gelu)):
+        close64(G.act_apply(x, name), fn(x))
+    assert G.ACTS == ("none", "relu", "tanh", "swish", "sigmoid", "gelu")
+    xg = x.clone().requires_grad_(True)
+    F.silu(xg).sum().backward()
+    close64(G.swish_grad(x), xg.grad)
+
+
+def test_rowsum_with_and_without_accumulate():
+    M, N, K = 5, 4, 13
+    a, b = R.randn(1, 1, M, K, seed=1).double(), R.randn(1, 1, N, K, seed=2).double()
+    old = R.randn(M + 16, seed=3).double()
+    for acc in (False, True):
+        p = _prob(G._dense_op(a, RC, False, False), G._dense_op(b, KC, False, False), M, N, K, a_rowsum_accumulate=acc,
+                  a_rowsum=NS(buf=old, off=8, ld=1, bs0=0, bs1=0, rows=M, N=1, nb0=1, nb1=1))
+        close64(G.gemm_ref(p, F64).rowsum, a[0, 0].sum(1) + (old[8:8 + M] if acc else 0))
+
+
+@pytest.mark.parametrize("Bu,T,ks,C", [(3, 5, 5, 4), (2, 9, 3, 6), (2, 7, 1, 3)])
+def test_conv1d_restatement_vs_torch_and_autograd(Bu, T, ks, C):
+    """Forward (A = implicit im2col, K-contiguous), data gradient (the same operand over dy with the flipped kernel) and weight gradient (B = the
+    row-contiguous im2col operand) of a 'same' Conv1d over Bu utterances of T frames, against F.conv1d and its autograd."""
+    O, pad = 5, ks // 2
+    x = R.randn(Bu, T, C, seed=1).double().requires_grad_(True)
+    w = R.randn(O, C, ks, seed=2).double().requires_grad_(True)
+    y = F.conv1d(x.transpose(1, 2), w, padding=pad).transpose(1, 2)                     # (Bu, T, O)
+    dy = R.randn(Bu, T, O, seed=3).double()
+    (y * dy).sum().backward()
+    geo = dict(T=T, pad=pad)
+    wm = w.detach().permute(0, 2, 1).reshape(1, 1, O, ks * C)                            # [o, j C + c] = w[o, c, j]
+    p = _prob(G._image_op(x.detach().reshape(Bu * T, C), KC, G.CONV1D, pad + 1, **geo), G._dense_op(wm, KC, False, False), Bu * T, O, ks * C)
+    close64(G.gemm_ref(p, F64).C[0, 0], y.detach().reshape(Bu * T, O))
+    wd = w.detach().flip(2).permute(1, 2, 0).reshape(1, 1, C, ks * O)                    # [c, j O + o] = w[o, c, ks - 1 - j]
+    p = _prob(G._image_op(dy.reshape(Bu * T, O), KC, G.CONV1D, pad + 1, **geo), G._dense_op(wd, RC, False, False), Bu * T, C, ks * O)
+    close64(G.gemm_ref(p, F64).C[0, 0], x.grad.reshape(Bu * T, C))
+    p = _prob(G._dense_op(dy.reshape(1, 1, Bu * T, O).transpose(2, 3).contiguous(), RC, False, False),
+              G._image_op(x.detach().reshape(Bu * T, C), RC, G.CONV1D, pad + 1, **geo), O, ks * C, Bu * T)
+    close64(G.gemm_ref(p, F64).C[0, 0], w.grad.permute(0, 2, 1).reshape(O, ks * C))
+
+
+@pytest.mark.parametrize("Bu,T2,F2,C", [(2, 2, 3, 4), (1, 3, 5, 2)])
+def test_conv2d_restatement_vs_torch_and_autograd(Bu, T2, F2, C):
+    O, T1, F1 = 3, 2 * T2 + 1, 2 * F2 + 2
+    x = R.randn(Bu, T1, F1, C, seed=1).double()
+    w = R.randn(O, C, 3, 3, seed=2).double().requires_grad_(True)
+    y = F.conv2d(x.permute(0, 3, 1, 2), w, stride=2).permute(0, 2, 3, 1)                 # (Bu, T2, F2, O)
+    assert y.shape == (Bu, T2, F2, O)
+    dy = R.randn(Bu, T2, F2, O, seed=3).double()
+    (y * dy).sum().backward()
+    geo = dict(T1=T1, F1=F1, T2=T2, F2=F2)
+    wm = w.detach().permute(0, 2, 3, 1).reshape(1, 1, O, 9 * C)                          # [o, (kh 3 + kw) C + c]
+    Mr = Bu * T2 * F2
+    p = _prob(G._image_op(x.reshape(-1, C), KC, G.CONV2D_S2, 1, **geo), G._dense_op(wm, KC, False, False), Mr, O, 9 * C)
+    close64(G.gemm_ref(p, F64).C[0, 0], y.detach().reshape(Mr, O))
+    p = _prob(G._dense_op(dy.reshape(1, 1, Mr, O).transpose(2, 3).contiguous(), RC, False, False), G._image_op(x.reshape(-1, C), RC, G.CONV2D_S2, 1, **geo),
+              O, 9 * C, Mr)
+    close64(G.gemm_ref(p, F64).C[0, 0], w.grad.permute(0, 2, 3, 1).reshape(O, 9 * C))
+
+
+@pytest.mark.parametrize("Tin,Fin", [(9, 12), (10, 11), (7, 7)])
+def test_tconv2d_classes_through_c_map_vs_conv2d_input_gradient(Tin, Fin):
+    """The four parity classes, each a GEMM over its class grid with the class matrix s2svc_tconv2d_weights lays out, stored through c_map:
+    together they are the input gradient of the 3 x 3 stride-2 convolution, every pixel written exactly once."""
+    Bu, C, O = 2, 3, 4
+    T2, F2 = (Tin - 3) // 2 + 1, (Fin - 3) // 2 + 1
+    x = R.randn(Bu, Tin, Fin, C, seed=1).double().requires_grad_(True)
+    w = R.randn(O, C, 3, 3, seed=2).double()
+    dy = R.randn(Bu, T2, F2, O, seed=3).double()
+    (F.conv2d(x.permute(0, 3, 1, 2), w, stride=2).permute(0, 2, 3, 1) * dy).sum().backward()
+    img = torch.full((Bu * Tin * Fin, C), G.NAN, dtype=F64)
+    hits = torch.zeros(Bu * Tin * Fin, dtype=torch.int64)
+    for pt in (0, 1):
+        for pf in (0, 1):
+            Tc, Fc, ntap = (Tin - pt + 1) // 2, (Fin - pf + 1) // 2, (2 - pt) * (2 - pf)
+            wc = torch.stack([w[:, :, pt + 2 * (tap // (2 - pf)), pf + 2 * (tap % (2 - pf))] for tap in range(ntap)], 0)     # (tap, o, c)
+            wc = wc.permute(2, 0, 1).reshape(1, 1, C, ntap * O)                                                           # [c, tap O + o]
+            A = G._image_op(dy.reshape(-1, O), KC, G.TCONV2D_S2, 1, T1=Tc, F1=Fc, T2=T2, F2=F2, pad=2 * pt + pf)
+            p = _prob(A, G._dense_op(wc, KC, False, False), Bu * Tc * Fc, C, ntap * O, c_map=(Tin, Fin, Tc, Fc, pt, pf), c_rows_total=Bu * Tin * Fin)
+            r = G.gemm_ref(p, F64)
+            img[r.rows] = r.C[0, 0]
+            hits[r.rows] += 1
+    assert bool((hits == 1).all())
+    close64(img, x.grad.reshape(-1, C))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the cases: sizes, exactness of the exact regime
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_case_table_is_well_formed():
+    assert len({c.name for c in G.CASES}) == len(G.CASES) > 150
+    for c in G.CASES:
+        assert G.madds(c) <= G.MAX_MADDS, (c.name, G.madds(c))
+        assert set(c.regimes) <= {"exact", "real"} and c.regimes
+        assert all(s in ("splitk_reduce", "stage_pass") for s in c.route.split("+")[1:]), c.route
+
+
+def _keep_for(c, regime):
+    return G.host_keep(c.M, c.N, c.drop_p, seed=G._seed_of(c, regime) + 11) if c.drop_p > 0 else None
+
+
+@pytest.mark.parametrize("group", list(G.GROUPS))
+def test_exact_regime_is_exact(group):
+    """For every exact case: |alpha| sum |a| |b| + |bias| + |res| + |previous C| < 2^24 on the actual tensors (so every partial sum in any order
+    is an exact fp32 value), and the float32 restatement equals the float64 one bit for bit -- the regime leaves a kernel no rounding to hide in."""
+    n = 0
+    for c in G.GROUPS[group]:
+        if "exact" not in c.regimes:
+            continue
+        p = G.problem(c, "exact")
+        assert G.exact_bound(p) < 2.0 ** 24, (c.name, G.exact_bound(p))
+        keep = _keep_for(c, "exact")
+        r64, r32 = G.gemm_ref(p, F64, keep), G.gemm_ref(p, F32, keep)
+        for a, b in ((r32.C, r64.C), (r32.c_pre, r64.c_pre), (r32.rowsum, r64.rowsum)):
+            assert (a is None) == (b is None)
+            if a is not None:
+                assert bool(torch.isfinite(b).all()), c.name                    # no poison reached a sum
+                assert R.bits_equal(a, b.to(F32)) and bool((b.to(F32).double() == b).all()), c.name
+        n += 1
+    assert n >= 4, group
+    for c in G.GROUPS[group]:                                                    # (the real regime reads no poison either)
+        if "real" in c.regimes and G.madds(c) < 2e7:
+            assert bool(torch.isfinite(G.gemm_ref(G.problem(c, "real"), F64, _keep_for(c, "real")).C).all()), c.name
+
+
+def test_grouped_recipes_are_exact_and_read_no_poison():
+    assert set(G.GROUPED) == {"grouped", "grouped_batched_kc", "grouped_batched_rc", "wgrad", "wgrad_conv2d", "wgrad_conv1d", "grouped_tconv"}
+    assert len(G.GROUPED["grouped"]) == 11                                      # two launches of 10
+    for cs in G.GROUPED.values():
+        for c in cs:
+            assert G.madds(c) <= G.MAX_MADDS
+            p = G.problem(c, "exact")
+            assert G.exact_bound(p) < 2.0 ** 24, c.name
+            r64, r32 = G.gemm_ref(p, F64), G.gemm_ref(p, F32)
+            assert bool(torch.isfinite(r64.C).all()) and R.bits_equal(r32.C, r64.C.to(F32)), c.name
+            if r64.rowsum is not None:
+                assert R.bits_equal(r32.rowsum, r64.rowsum.to(F32)), c.name
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the power check
+# ---------------------------------------------------------------------------------------------------------------------------
+def _outputs(c, p, r):
+    """What the GPU case compares, as one flat tensor per output: C as the image of all its rows (unwritten rows: NaN), c_pre, a_rowsum."""
+    rows_total = p.Cbuf.rows + (p.c_map[1] if p.c_map is not None else 0)          # (room for a planted row map that overshoots)
+    img = torch.full((p.nb0, p.nb1, rows_total, p.N), G.NAN, dtype=r.C.dtype)
+    img[:, :, r.rows] = r.C
+    out = [("C", img, p.c_dtype)]
+    if r.rowsum is not None:
+        out.append(("a_rowsum", r.rowsum, F32))
+    return out
+
+
+def plant_verdict(c, regime, plant):
+    """-> (caught, need): does the planted float64 result fail the rule the GPU case applies to these inputs?  need: the margin it would take
+    (real regime: (|planted - ref64| - ulp) / d at the worst element; exact regime: inf when a bit differs)."""
+    p = G.problem(c, regime)
+    keep = _keep_for(c, regime)
+    r64, bad = G.gemm_ref(p, F64, keep), G.gemm_ref(p, F64, keep, plant=plant)
+    yard = G.gemm_ref(p, F32, keep) if regime == "real" else None
+    caught, need = False, 0.0
+    for i, (name, ref, odt) in enumerate(_outputs(c, p, r64)):
+        got = _outputs(c, p, bad)[i][1]
+        written = ~torch.isnan(ref)
+        if regime == "exact":
+            same = R.bits_equal(got.to(odt), ref.to(odt))
+            caught, need = caught or not same, max(need, 0.0 if same else float("inf"))
+            continue
+        if not bool((torch.isnan(got) == ~written).all()):                       # another set of rows was written
+            caught, need = True, float("inf")
+            continue
+        yd = _outputs(c, p, yard)[i][1]
+        ok, _, d, _ = R.compare(got[written], ref[written], yd[written], odt)
+        err = (got[written] - ref[written]).abs() - R.ulp_out(ref[written], odt)
+        caught, need = caught or not ok, max(need, float(err.max()) / d if d > 0 else float("inf"))
+    return caught, need
+
+
+def plant_table(limit_madds=3e7):
+    """[(plant, case name, regime, caught, need)] for every plant and every case it applies to (below limit_madds)."""
+    rows = []
+    for c in G.CASES:
+        if G.madds(c) > limit_madds:
+            continue
+        for plant in G.plants_of(c):
+            for regime in c.regimes:
+                rows.append((plant, c.name, regime) + plant_verdict(c, regime, plant))
+    return rows
+
+
+def test_every_plant_is_caught_on_the_inputs_of_the_gpu_cases():
+    rows = plant_table()
+    assert {r[0] for r in rows} == set(G.PLANTS), set(G.PLANTS) - {r[0] for r in rows}
+    missed = [r for r in rows if not r[3]]
+    # Real inputs: every case a plant applies to catches it.  Exact inputs: a dropped term can leave an integer result as it was (a row sum
+    # that is 0, a ReLU that hides the row), so here every plant is caught by most cases it applies to and never by none.
+    assert not [r for r in missed if r[2] == "real"], [r for r in missed if r[2] == "real"]
+    assert all(r[4] > R.MARGIN for r in rows if r[2] == "real")
+    for plant in G.PLANTS:
+        ex = [r for r in rows if r[0] == plant and r[2] == "exact"]
+        assert ex and [r for r in rows if r[0] == plant and r[2] == "real"], plant
+        assert sum(r[3] for r in ex) >= max(1, 0.9 * len(ex)), (plant, [r for r in ex if not r[3]])
+
+
+def test_a_plant_on_a_case_it_does_not_apply_to_changes_nothing():
+    """(the control of the power check: the comparison is not failing on its own)"""
+    c = next(c for c in G.CASES if c.name == "glds_bm32/lean_k64")
+    for regime in c.regimes:
+        p = G.problem(c, regime)
+        r64, yard = G.gemm_ref(p, F64), G.gemm_ref(p, F32)
+        assert R.compare(r64.C.to(BF16), r64.C, yard.C, BF16)[0]
+        assert R.bits_equal(G.gemm_ref(p, F64, plant="tap_across_utt").C, r64.C)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the route table
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_every_route_name_in_the_sources_is_claimed_by_a_case_or_excused():
+    names, adds = G.routes_in_sources(os.path.join(ROOT, "seq2seq_vc_amd", "csrc"))
+    assert len(names) > 100 and adds == {"+splitk_reduce", "+stage_pass"}, (len(names), adds)
+    # every launch site of the five files that s2svc_gemm can reach names its kernel: the launcher functions below are the grouped / weight-
+    # gradient entry points and the class-weight layout, which take no route
+    unnamed_ok = ("tconv2d_weights", "gemm_grouped", "gemm_8ph_tr_grouped_kernel", "gemm_w8ls_kernel", "w8_reduce_kernel")
+    for f in ("gemm.hip", "gemm_fast.hip", "gemm_glds.hip", "gemm_8ph.hip", "gemm_skinny.hip"):
+        src = open(os.path.join(ROOT, "seq2seq_vc_amd", "csrc", f)).read().replace("\\\n", " ")
+        for m in re.finditer(r"hipLaunchKernelGGL\(\(?\s*(\w+)", src):
+            if m.group(1).startswith(unnamed_ok) or m.group(1) == "KERNEL":
+                continue
+            before = src[max(0, m.start() - 900):m.start()]
+            assert "s2s_gemm_route" in before or "S2S_FAST_ROUTE" in before, f"{f}: the launch of {m.group(1)} names no route"
+    claimed, claimed_adds = set(), set()
+    for c in G.CASES:
+        parts = c.route.split("+")
+        claimed.add(parts[0])
+        claimed_adds |= {"+" + s for s in parts[1:]}
+    assert claimed <= names, f"cases written for route names no launch site reports: {sorted(claimed - names)}"
+    assert not set(G.UNREACHABLE) & claimed, sorted(set(G.UNREACHABLE) & claimed)
+    assert set(G.UNREACHABLE) <= names, sorted(set(G.UNREACHABLE) - names)
+    for name, why in G.UNREACHABLE.items():
+        assert why.startswith("unreachable on this build: constexpr switch "), name
+    missing = names - claimed - set(G.UNREACHABLE)
+    assert not missing, f"route names without a case (add one to tests/gemm_kernels_ref.py): {sorted(missing)}"
+    assert claimed_adds == adds
+
+
+def test_unreachable_reasons_name_live_switches():
+    """The constexpr switches the excuses lean on still have the values they name."""
+    src = open(os.path.join(ROOT, "seq2seq_vc_amd", "csrc", "gemm_glds.hip")).read()
+    for decl in ("constexpr bool k2_enabled() { return true; }", "constexpr int k2_min_tiles() { return 12; }", "constexpr int deep_min_tiles() { return 16; }",
+                 "constexpr bool tr_enabled() { return true; }", "constexpr int dma_stages() { return 0; }"):
+        assert decl in src, decl

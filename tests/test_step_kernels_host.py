@@ -315,6 +315,7 @@ LEDGER = {
     "s2svc_event_destroy": ("not a kernel", "hipEventDestroy"),
     "s2svc_event_record": ("not a kernel", "hipEventRecord"),
     "s2svc_stream_wait_event": ("not a kernel", "hipStreamWaitEvent"),
+    "s2svc_gemm_last_route": ("not a kernel", "returns the name of the kernel the last s2svc_gemm call launched; gpu_gemm_kernel_check holds every case to it"),
     "s2svc_launch_floor": ("not a kernel", "launches a kernel that computes nothing: a timing probe of tools/ and bench.py"),
     "s2svc_gl_supported": ("not a kernel", "host-side size query; test_griffin_lim_host pins its table"),
     "s2svc_hifigan_cin_padded": ("not a kernel", "host-side padding query of the vocoder's weight layout"),
@@ -322,7 +323,6 @@ LEDGER = {
     "s2svc_dwconv": ("case", "gpu_kernel_check_aas", "depthwise_conv"),                       # = s2svc_dwconv_add with add = NULL
     "s2svc_add_head_bias_ld": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
     "s2svc_add_rows": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_gemm_grouped_batched": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
     "s2svc_bn_stats_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_bn_act_apply_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_bn_act_bwd_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
@@ -460,3 +460,8 @@ def test_every_launcher_has_a_kernel_level_check():
     for sym in ("s2svc_attn_fused_supported", "s2svc_attn_fused_fwd", "s2svc_attn_fused_bwd", "s2svc_attn_map_supported", "s2svc_attn_map_product_supported",
                 "s2svc_attn_map_fwd", "s2svc_attn_map_bwd", "s2svc_relattn_supported", "s2svc_relattn_fwd", "s2svc_attn_softmax_fwd", "s2svc_attn_softmax_bwd"):
         assert re.search(r"\b%s\(" % sym, attn[0]) or any(_called_in(attn, w) for w in wrappers[sym]), f"{sym} is no longer called by tests/gpu_attn_kernel_check.py"
+    # ... and the GEMM families in tests/gpu_gemm_kernel_check.py
+    gemm = mods["gpu_gemm_kernel_check"]
+    for sym in ("s2svc_gemm", "s2svc_gemm_grouped", "s2svc_gemm_grouped_ok", "s2svc_gemm_grouped_batched", "s2svc_gemm_wgrad_ok", "s2svc_gemm_wgrad_ws_floats",
+                "s2svc_gemm_wgrad_grouped", "s2svc_gemm_wgrad_grouped_bg", "s2svc_gemm_set_w8", "s2svc_gemm_set_8ph", "s2svc_tconv2d_weights"):
+        assert re.search(r"\b%s\(" % sym, gemm[0]), f"{sym} is no longer called by name in tests/gpu_gemm_kernel_check.py"
