@@ -387,6 +387,11 @@ int s2svc_interp_nearest(int dtype, int B, int Tin, int Tout, int C, const void*
                          const int32_t* ext_out, void* stream);
 int s2svc_interp_nearest_bwd(int dtype, int B, int Tin, int Tout, int C, const void* dy, void* dx, const int32_t* ext_in,
                              const int32_t* ext_out, void* stream);
+/* The same resampling with one pair of lengths PER ROW (lens_in / lens_out: B int32 each, device) -- inference on a padded batch of
+   utterances of different lengths (AASVC.inference_batch): replaces the per-utterance F.interpolate of models/aas_vc.py:345-350 with
+   each row's own ratio lens_in[b] / lens_out[b]; output frames >= lens_out[b] are zero, input frames >= lens_in[b] never read.  No backward. */
+int s2svc_interp_nearest_rows(int dtype, int B, int Tin, int Tout, int C, const void* x, void* y, const int32_t* lens_in,
+                              const int32_t* lens_out, void* stream);
 int s2svc_dwconv(int dtype, int B, int Tn, int C, int ks, int dil, const void* x, const float* w, const float* bias,
                  void* y, int flip, void* stream);
 /* y = dwconv(x) + add (add: a tensor of y's shape or NULL): the data gradient of a depthwise convolution whose input also feeds a
@@ -418,6 +423,21 @@ int s2svc_convmod_bwd(int B, int Tn, int C, int ks, const void* da, const void* 
                       const float* rstd, const float* gamma, const float* beta, void* dy2, float* sdy, float* sdyx,
                       float* dgamma_acc, float* dbeta_acc, float* ws_stats, float* ws_w, const int32_t* vlens, void* stream);
 int s2svc_convmod_wgrad_final(int C, int ks, int chunks, const float* ws_w, float* dw, float* db, int accumulate, void* stream);
+
+/* Core of the Conformer convolution module in INFERENCE mode, fp32 or bf16, one launch, per-row lengths (csrc/convmod_infer.hip):
+   GLU -> depthwise conv -> BatchNorm1d with its running statistics -> Swish between the two pointwise convolutions.
+   replaces: modules/conformer/convolution.py:68-75 (glu, depthwise_conv, norm, activation) in eval().
+     y2 (B,Tn,2C) = output of pointwise_conv1 in `dtype`;  w (C,1,ks) fp32, bias (C) or NULL;  run_mean / run_var (C);  gamma / beta (C) or
+     NULL (1 / 0);  out (B,Tn,C) in `dtype`;  vlens (B int32) or NULL (every row is full):
+       out[b,t,c] = swish(((bias[c] + sum_j w[c,j] g[b,t+j-(ks-1)/2,c]) - run_mean[c]) / sqrt(run_var[c] + eps) * gamma[c] + beta[c]),  t < vlens[b]
+       out[b,t,c] = 0,  t >= vlens[b];      g = glu(y2) at frames 0 <= t' < vlens[b], 0 elsewhere.
+     Frames >= vlens[b] of y2 are never read (they may hold anything, NaN included); every element of out is written exactly once;
+     fp32 accumulation in a fixed order, no atomics, no workspace.  y2 and out 16-byte aligned, B * ceil(Tn / 64) <= 65535.
+   s2svc_convmod_infer_supported: C % 8 == 0 and odd ks <= 31; everything else takes the separate kernels. */
+int s2svc_convmod_infer_supported(int C, int ks);
+int s2svc_convmod_infer(int dtype, int B, int Tn, int C, int ks, const void* y2, const float* w, const float* bias, const float* run_mean,
+                        const float* run_var, const float* gamma, const float* beta, float eps, void* out, const int32_t* vlens,
+                        void* stream);
 
 /* BatchNorm1d (training mode) + activation + dropout on channel-last bf16 rows, C % 8 == 0, 16-byte accesses (csrc/convmod.hip).
    replaces: modules/pre_postnets.py:108-165 (BatchNorm1d -> Tanh -> Dropout of the Postnet layers) and its autograd backward.
@@ -467,6 +487,14 @@ int s2svc_length_regulate_index(int B, int Tx, int Tout, const int32_t* ds, int3
                                 void* stream);
 int s2svc_length_regulate_fwd(int dtype, int B, int Tx, int Tout, int D, const void* x, const int32_t* idx, float pad_value,
                               void* y, void* stream);
+/* Predicted durations -> the length regulator's input, per row of a padded batch, one wave per row (csrc/lenreg.hip).
+   replaces: models/aas_vc.py:393 (clamp at MAX_DP_OUTPUT) + modules/length_regulator.py:127-135 (ds[ds.sum(dim=1).eq(0)] = 1 on the
+   single-utterance tensor) + the two host reads of the duration sum that sized the output.
+     d (B,Tx) fp32 (dtype_i64 = 0) or int64 (1), integers in value;  text_lens (B int32);  dmax: the clamp (dmax * Tx < 2^24);
+     d_outs (B,Tx) in d's type = min(d, dmax), 0 at entries >= text_lens[b] (those entries of d are never read);
+     ds (B,Tx) fp32 = d_outs, except that a row whose valid entries sum to 0 holds 1 in every VALID entry;  total (B int32) = row sums of ds. */
+int s2svc_durations_finalize(int dtype_i64, int B, int Tx, const void* d, const int32_t* text_lens, float dmax, void* d_outs, float* ds,
+                             int32_t* total, void* stream);
 int s2svc_length_regulate_bwd(int dtype, int B, int Tx, int Tout, int D, const void* dy, const int32_t* start, const int32_t* ds,
                               void* dx, void* stream);
 /* Durations from attention maps -- replaces utils/duration_calculator.py:13-65: att (NH, Tf, Tx) fp32 (NH = layers * heads,

@@ -31,6 +31,17 @@ class ConvolutionModule(nn.Module):
         c1, c2, bn = self.pointwise_conv1, self.pointwise_conv2, self.norm
         vl = Mo.crop_dev(lens) if self.training else None
         y = Fn.linear(x, c1.weight, c1.bias)           # 1x1 conv == Linear on channel-last ((N,K,1) weight accepted)
+        rl = None if self.training else Mo.rows_dev(lens)
+        if rl is not None:
+            # batched inference with per-row lengths (Lens.per_row): frames beyond a row's own length are the convolution's zero padding
+            if FA.convmod_infer_ok(y, self.depthwise_conv.weight, self.activation):      # one launch (csrc/convmod_infer.hip)
+                y = FA.convmod_infer(y, self.depthwise_conv.weight, self.depthwise_conv.bias, bn.weight, bn.bias, bn.running_mean,
+                                     bn.running_var, bn.eps, vlens=rl)
+            else:
+                y = FA.dwconv1d(Fn.crop_rows(Fn.glu(y), rl), self.depthwise_conv.weight, self.depthwise_conv.bias)
+                y = Fn.batch_norm_act(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, False,
+                                      self.activation, 0.0, bn.eps, bn.momentum)
+            return Fn.linear(y, c2.weight, c2.bias)
         if FA.convmod_core_ok(y, self.depthwise_conv.weight, self.training, self.activation):
             # bf16 training: GLU -> depthwise conv -> batch statistics -> BatchNorm + Swish on the fused kernels (csrc/convmod.hip)
             y = FA.convmod_core(y, self.depthwise_conv.weight, self.depthwise_conv.bias, bn.weight, bn.bias, bn.running_mean,

@@ -127,6 +127,28 @@ __global__ void interp_nearest_bwd_kernel(int B, int Tin_cap, int Tout_cap, int 
   }
 }
 
+// the same resampling with one pair of lengths PER ROW of a padded batch (inference on utterances of different lengths): row b is what
+// F.interpolate gives on its own lin[b] frames for an output of lout[b] frames; output frames >= lout[b] are zero, input frames >= lin[b]
+// are never read
+template <typename T>
+__global__ void interp_nearest_rows_kernel(int B, int Tin_cap, int Tout_cap, int C, const T* __restrict__ x, T* __restrict__ y,
+                                           const int32_t* __restrict__ lin, const int32_t* __restrict__ lout) {
+  const int64_t n = (int64_t)B * Tout_cap * C;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const int64_t r = i / C;
+    const int t = (int)(r % Tout_cap);
+    const int b = (int)(r / Tout_cap);
+    const int Tin = lin[b] < Tin_cap ? (lin[b] > 0 ? lin[b] : 1) : Tin_cap;
+    const int Tout = lout[b] < Tout_cap ? (lout[b] > 0 ? lout[b] : 0) : Tout_cap;
+    if (t >= Tout) { stf(y + i, 0.f); continue; }
+    const float scale = (float)Tin / (float)Tout;
+    int src = (int)floorf((float)t * scale);
+    if (src > Tin - 1) src = Tin - 1;
+    y[i] = x[((int64_t)b * Tin_cap + src) * C + c];
+  }
+}
+
 inline int ew_blocks(int64_t total) {
   int64_t b = (total + 255) / 256;
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
@@ -159,6 +181,20 @@ extern "C" int s2svc_interp_nearest(int dtype, int B, int Tin, int Tout, int C, 
   else
     hipLaunchKernelGGL(interp_nearest_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, B, Tin, Tout, C, (const bf16_t*)x, (bf16_t*)y, ext_in, ext_out);
   S2S_CHECK_LAUNCH("interp_nearest_kernel");
+  return 0;
+}
+
+extern "C" int s2svc_interp_nearest_rows(int dtype, int B, int Tin, int Tout, int C, const void* x, void* y, const int32_t* lens_in,
+                                         const int32_t* lens_out, void* stream) {
+  const int64_t n = (int64_t)B * Tout * C;
+  if (n == 0) return 0;
+  S2S_REQUIRE(Tin > 0 && x && y && lens_in && lens_out, "interp_nearest_rows: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == S2S_F32)
+    hipLaunchKernelGGL(interp_nearest_rows_kernel<float>, dim3(ew_blocks(n)), dim3(256), 0, st, B, Tin, Tout, C, (const float*)x, (float*)y, lens_in, lens_out);
+  else
+    hipLaunchKernelGGL(interp_nearest_rows_kernel<bf16_t>, dim3(ew_blocks(n)), dim3(256), 0, st, B, Tin, Tout, C, (const bf16_t*)x, (bf16_t*)y, lens_in, lens_out);
+  S2S_CHECK_LAUNCH("interp_nearest_rows_kernel");
   return 0;
 }
 

@@ -8,6 +8,9 @@
 //   * s2svc_attn_durations: replaces utils/duration_calculator.py:13-65 for the Transformer case: picks the most diagonal
 //     attention head (largest mean over output frames of the row maximum), counts for every input position how many output
 //     frames have their arg-max there, and reports the focus rate.
+//   * s2svc_durations_finalize: replaces models/aas_vc.py:393 + modules/length_regulator.py:127-135 of the inference path, per row of
+//     a padded batch: clamp, clear the entries beyond the row's text length, give an all-zero row 1 in every valid entry, row totals --
+//     on the device, so that sizing the regulator's output costs one read of B ints instead of two stream stops.
 #include "common.h"
 #include "../../include/s2svc_hip.h"
 
@@ -134,6 +137,36 @@ __global__ __launch_bounds__(256) void attn_durations_kernel(int NH, int Tf, int
   }
 }
 
+// one wave per utterance; the durations are integers in value (<= dmax after the clamp), so the fp32 sums are exact
+template <typename TD>
+__global__ __launch_bounds__(64) void durations_finalize_kernel(int Tx, const TD* __restrict__ d, const int32_t* __restrict__ text_lens, float dmax,
+                                                                TD* __restrict__ d_outs, float* __restrict__ ds, int32_t* __restrict__ total) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int L = text_lens[b] < 0 ? 0 : (text_lens[b] < Tx ? text_lens[b] : Tx);
+  const TD* db = d + (int64_t)b * Tx;
+  float part = 0.f;
+  for (int i = lane; i < Tx; i += 64) {          // entries >= L are never read
+    float v = 0.f;
+    if (i < L) {
+      v = (float)db[i];
+      v = v > dmax ? dmax : v;
+    }
+    d_outs[(int64_t)b * Tx + i] = (TD)v;
+    part += v;
+  }
+  const float sum = wave_sum(part);              // all 64 lanes are here; same partners in the same order on every call
+  const bool none = sum == 0.f;                  // reference: ds[ds.sum(dim=1).eq(0)] = 1 on a (1, Tx) tensor
+  for (int i = lane; i < Tx; i += 64) {
+    float v = 0.f;
+    if (i < L) {
+      v = (float)db[i];
+      v = none ? 1.f : (v > dmax ? dmax : v);
+    }
+    ds[(int64_t)b * Tx + i] = v;
+  }
+  if (lane == 0) total[b] = none ? L : (int32_t)sum;
+}
+
 inline int lr_blocks(int64_t total) {
   int64_t b = (total + 255) / 256;
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -183,6 +216,19 @@ extern "C" int s2svc_length_regulate_bwd(int dtype, int B, int Tx, int Tout, int
   else
     hipLaunchKernelGGL(lr_bwd_kernel<bf16_t>, dim3(lr_blocks(n)), dim3(256), 0, st, n, Tx, Tout, D, (const bf16_t*)dy, start, ds, (bf16_t*)dx);
   S2S_CHECK_LAUNCH("lr_bwd_kernel");
+  return 0;
+}
+
+extern "C" int s2svc_durations_finalize(int dtype_i64, int B, int Tx, const void* d, const int32_t* text_lens, float dmax, void* d_outs, float* ds,
+                                        int32_t* total, void* stream) {
+  S2S_REQUIRE(B > 0 && Tx > 0 && d && text_lens && d_outs && ds && total, "durations_finalize: bad args");
+  S2S_REQUIRE(dmax >= 0.f && (double)dmax * Tx < 16777216.0, "durations_finalize: row sums must stay exact in fp32");
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype_i64)
+    hipLaunchKernelGGL(durations_finalize_kernel<int64_t>, dim3(B), dim3(64), 0, st, Tx, (const int64_t*)d, text_lens, dmax, (int64_t*)d_outs, ds, total);
+  else
+    hipLaunchKernelGGL(durations_finalize_kernel<float>, dim3(B), dim3(64), 0, st, Tx, (const float*)d, text_lens, dmax, (float*)d_outs, ds, total);
+  S2S_CHECK_LAUNCH("durations_finalize_kernel");
   return 0;
 }
 

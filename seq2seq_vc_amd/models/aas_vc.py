@@ -367,3 +367,86 @@ class AASVC(nn.Module):
         if ret["ds"] is None and ret["log_p_attn"] is None:
             return outs[0].float(), d_outs[0]
         return outs[0].float(), d_outs[0], ret["ds"][0], ret["log_p_attn"][0], ret["ilens"][0]
+
+    @torch.no_grad()
+    def inference_batch(self, xs, ilens, dp_inputs=None, dplens=None, spembs=None, *, tgt_speech=None, use_teacher_forcing=False):
+        """Several utterances in one pass: xs (B, Tmax, idim) padded, ilens (B,); dp_inputs (B, Dmax, dp_idim) with dplens (default: ilens)
+        when the duration predictor has its own input.  -> (outs (B, Lmax, odim) fp32, exactly zero beyond olens[b]; olens (B,) LongTensor on
+        the host; d_outs (B, Tx)).
+
+        Extension: the reference converts utterance by utterance (bin/vc_decode.py:264-306); its batched `_forward(is_inference=True)`
+        masks nothing in the decoder, sums the durations over the whole batch and lets padding into the convolution modules and the
+        Postnet.  The contract here is the one of VTN.inference_batch: EACH ROW IS GIVEN WHAT IT HAS WHEN PROCESSED ALONE --
+        row b equals inference(xs[b, :ilens[b]], dp_input=dp_inputs[b, :dplens[b]]).  Whatever lies beyond a row's length is ignored (it
+        is cleared on the way in and every stage that mixes along time gets the per-row lengths, modules.Lens.per_row); an injected
+        `duration_predictor.noise` (B, 2, Tx) is used row by row, its first Tx_b columns.  One device-to-host read (B ints: the row
+        totals of the durations, which size the output) where `inference` stops the stream twice."""
+        if tgt_speech is not None:
+            raise NotImplementedError("a target utterance is the reference's debug path (alignment + durations): use inference()")
+        if use_teacher_forcing:
+            raise NotImplementedError("teacher-forced inference is broken in the reference (models/aas_vc.py:572) and unused")
+        if spembs is not None:
+            raise NotImplementedError("speaker-embedding integration is out of scope (no recipe config uses it)")
+        if Mo._BANK is not None:
+            raise RuntimeError("inference_batch inside a captured training step")
+        own_dp = not self.duration_predictor_use_encoder_outputs
+        if own_dp and dp_inputs is None:
+            raise ValueError("this model's duration predictor has its own input: pass dp_inputs (and dplens)")
+        dev = xs.device
+        B = xs.shape[0]
+        er, pr, dr = self.encoder_reduction_factor, self.post_encoder_reduction_factor, self.decoder_reduction_factor
+        il = Mo.Lens.of(ilens, dev).per_row()
+        if len(il.host) != B or min(il.host) < 1 or max(il.host) > xs.shape[1]:
+            raise ValueError(f"ilens {list(il.host)} do not fit xs of shape {tuple(xs.shape)}")
+        xs = Fn.crop_rows(Fn.to_compute(xs[:, : il.max()]), il.dev)             # the padding may hold anything: cleared here
+        if er > 1:
+            b, tmax, dim = xs.shape
+            if tmax % er != 0:
+                xs = xs[:, : -(tmax % er)]
+            xs = xs.contiguous().view(b, tmax // er, dim * er)
+            il = il.map(lambda v: v // er)
+        hs, hl = self.encoder(xs, il, exact_lens=True)
+        if self.encoder_input_layer == "conv2d":
+            il = hl
+        if pr > 1:
+            b, tmax, dim = hs.shape
+            if tmax % pr != 0:
+                hs = hs[:, : -(tmax % pr)]                                   # a row's own trailing T_b % pr frames lie beyond il // pr
+            hs = hs.contiguous().view(b, tmax // pr, dim * pr)
+            il = il.map(lambda v: v // pr)
+        Tx = hs.shape[1]
+        il_c = il.clamp(Tx)
+        if min(il_c.host) < 1:
+            raise ValueError(f"an utterance is too short: encoder output lengths {list(il_c.host)}")
+        if own_dp:
+            dl = Mo.Lens.of(ilens if dplens is None else dplens, dev).per_row()
+            if len(dl.host) != B or min(dl.host) < 1 or max(dl.host) > dp_inputs.shape[1]:
+                raise ValueError(f"dplens {list(dl.host)} do not fit dp_inputs of shape {tuple(dp_inputs.shape)}")
+            d = Fn.crop_rows(Fn.to_compute(dp_inputs[:, : dl.max()]), dl.dev)
+            d, dl = self.duration_predictor_projection(d, dl, exact_lens=True)
+            if min(dl.host) < 1:
+                raise ValueError(f"a duration-predictor input is too short: projected lengths {list(dl.host)}")
+            dpi = FA.interp_nearest_rows(d, Tx, dl.dev, il_c.dev)               # every row at the ratio of its own single call
+        else:
+            dpi = hs
+        if self.duration_predictor_type == "stochastic":
+            sdp = self.duration_predictor
+            if sdp.noise is not None:                                       # injected draw: row b uses its first Tx_b columns
+                n = sdp.noise.to(device=dev, dtype=torch.float32)
+                if n.shape != (B, 2, Tx):
+                    raise ValueError(f"duration_predictor.noise has shape {tuple(n.shape)}, the batch needs {(B, 2, Tx)}")
+                keep = torch.arange(Tx, device=dev)[None, None, :] < il_c.dev[:, None, None]
+                sdp.noise = torch.where(keep, n, torch.zeros((), device=dev))
+            d_raw = sdp.forward_cl(dpi, il_c, inverse=True, noise_scale=self.stochastic_duration_predictor_noise_scale)
+        else:
+            d_raw = self.duration_predictor.inference(dpi, il_c)
+        d_outs, ds, total = FA.durations_finalize(d_raw.contiguous(), il_c.dev, MAX_DP_OUTPUT)
+        totals = total.tolist()                                              # the one host read: it sizes the output
+        fl = Mo.Lens(totals, dev).per_row()
+        hs = self.length_regulator(hs, ds, fl, il_c, fl.max())
+        zs, _ = self.decoder(hs, fl)
+        before = Fn.linear(zs, self.feat_out.weight, self.feat_out.bias).view(B, -1, self.odim)
+        ol = fl if dr == 1 else fl.map(lambda v, _r=dr: v * _r)
+        after = before if self.postnet is None else Fn.add_dropout(before, self.postnet(before, ol), 0.0)
+        outs = Fn.crop_rows(after, ol.dev).float()
+        return outs, torch.tensor(list(ol.host), dtype=torch.long), d_outs

@@ -152,6 +152,7 @@ class Lens:
         self.device = torch.device(device)
         self.cap = None
         self.ext = None               # no bank: the models crop the batch themselves, every row of a tensor is present
+        self.rows = False             # per_row(): every row ends at its OWN length (batched inference)
         key = (self.host, self.device.type, self.device.index)
         t = _LENS_CACHE.get(key)
         if t is None:
@@ -167,6 +168,7 @@ class Lens:
         self.cap = int(cap)
         self.ext = int(max(self.host) if ext is None else ext)      # a root: the reference crops to the longest utterance
         self._crop = None
+        self.rows = False
         self.dev = bank._slot(self, source)
 
     @staticmethod
@@ -193,9 +195,18 @@ class Lens:
             vals, ext = _derive(("map", self, fn, ext_fn, with_ext), len(self.host))
             return Lens(vals, self.device, _source=("map", self, fn, ext_fn, with_ext), _cap=(ext_fn if ext_fn is not None else fn)(self.cap),
                         _ext=ext)
-        if with_ext:
-            return Lens([fn(v, self.max()) for v in self.host], self.device)
-        return Lens([fn(v) for v in self.host], self.device)
+        out = Lens([fn(v, self.max()) for v in self.host] if with_ext else [fn(v) for v in self.host], self.device)
+        out.rows = self.rows
+        return out
+
+    def per_row(self):
+        """These lengths as PER-ROW lengths of a padded batch in inference: frames t >= host[b] of row b are absent for every module
+        that mixes along time (crop_dev / rows_dev give the device vector), so that row b is what its utterance gives when it is
+        processed alone (models: inference_batch).  Derived lengths (map, clamp) keep the property.  Not for captured steps."""
+        assert self.cap is None, "per-row lengths are an inference feature: no LensBank"
+        out = Lens(self.host, self.device)
+        out.rows = True
+        return out
 
     def crop(self):
         """The `vlens` of the kernels that must not see the frames between the reference's cropped length and the padded length
@@ -214,10 +225,18 @@ class Lens:
 
 
 def crop_dev(lens):
-    """Device vector for the `vlens` argument of the time-mixing kernels, or None (no bank / no lengths)."""
-    if lens is None or lens.cap is None:
+    """Device vector for the `vlens` argument of the time-mixing kernels, or None (no bank / no lengths).  Per-row inference lengths
+    (Lens.per_row) are their own vector."""
+    if lens is None:
         return None
+    if lens.cap is None:
+        return lens.dev if lens.rows else None
     return lens.crop().dev
+
+
+def rows_dev(lens):
+    """The device vector of per-row inference lengths (Lens.per_row), None for every other Lens."""
+    return lens.dev if lens is not None and lens.cap is None and lens.rows else None
 
 
 # ------------------------------------------------------------------------------------------------

@@ -136,6 +136,23 @@ def convmod_core_ok(y2, dw_weight, training, activation):
             and dw_weight.shape[1] == 1 and KA.convmod_supported(dw_weight.shape[0], dw_weight.shape[-1]))
 
 
+def convmod_infer_ok(y2, dw_weight, activation):
+    """The one-launch inference core (csrc/convmod_infer.hip) can take this module: Swish, a depthwise weight (C, 1, ks) of a supported
+    shape, no autograd graph to build (it has no backward pass).  S2SVC_NO_CONVMOD_INFER=1 (read per call) keeps the separate launches."""
+    import os
+    return (activation == "swish" and not torch.is_grad_enabled() and y2.dtype in (torch.float32, torch.bfloat16)
+            and os.environ.get("S2SVC_NO_CONVMOD_INFER", "0") != "1" and dw_weight.shape[1] == 1
+            and KA.convmod_infer_supported(dw_weight.shape[0], dw_weight.shape[-1]))
+
+
+def convmod_infer(y2, dw_weight, dw_bias, gamma, beta, run_mean, run_var, eps=1e-5, vlens=None):
+    """swish(batch_norm(dwconv1d(glu(y2)))) with BatchNorm1d's running statistics, one launch, under no_grad; use convmod_infer_ok()
+    first.  vlens (B int32, device): frames t >= vlens[b] are absent -- zero padding on the way in, zero on the way out -- so row b is
+    what its utterance gives when it is processed alone."""
+    return KA.convmod_infer(_c(y2), dw_weight.detach(), None if dw_bias is None else dw_bias.detach(), run_mean, run_var,
+                            None if gamma is None else gamma.detach(), None if beta is None else beta.detach(), eps, vlens=vlens)
+
+
 class _PairwiseLogSoftmax(Function):
     """log_p_attn[b,i,:] = log_softmax_j(-||feats[b,i]-text[b,j]||_2), padded text columns -inf
     (modules/alignments.py:51-59)."""
@@ -270,6 +287,20 @@ def interp_nearest(x, Tout, ext_in=None, ext_out=None):
     """F.interpolate(x^T, size=Tout)^T per batch item on channel-last (B, T, C)  (models/aas_vc.py:340-349).
     ext_in / ext_out: the cropped lengths as graph data when the tensors are padded (captured steps), see kernels.interp_nearest."""
     return _InterpNearest.apply(x, Tout, ext_in, ext_out)
+
+
+def interp_nearest_rows(x, Tout, lens_in, lens_out):
+    """interp_nearest with one (input length, output length) pair per row of a padded batch (B int32 device tensors): every row sees the
+    ratio of its own single call.  Inference only (no backward pass)."""
+    assert not (torch.is_grad_enabled() and x.requires_grad), "interp_nearest_rows has no backward pass"
+    return K.interp_nearest_rows(_c(x), Tout, lens_in, lens_out)
+
+
+def durations_finalize(d, text_lens_i32, dmax):
+    """Predicted durations (B, Tx) fp32 / int64 of a padded batch -> (d_outs: clamped at dmax, 0 beyond text_lens[b]; ds fp32: the length
+    regulator's input -- a row whose valid entries sum to 0 gets 1 in every valid entry; total (B) int32: row sums of ds).  One launch,
+    on the device (csrc/lenreg.hip); no gradient (predicted durations carry none)."""
+    return KA.durations_finalize(_c(d.detach()), text_lens_i32, dmax)
 
 
 class _LengthRegulate(Function):

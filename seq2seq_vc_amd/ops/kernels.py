@@ -1194,6 +1194,16 @@ def interp_nearest(x, Tout, ext_in=None, ext_out=None):
     return y
 
 
+def interp_nearest_rows(x, Tout, lens_in, lens_out):
+    """Nearest-neighbour resampling with one (input length, output length) pair per row (int32 device tensors of B entries): row b is
+    what F.interpolate makes of its own lens_in[b] frames for lens_out[b] output frames; zero beyond (include/s2svc_hip.h).  Inference only."""
+    B, Tin, C = x.shape
+    y = torch.empty((B, Tout, C), dtype=x.dtype, device=x.device)
+    _lib.check(_lib.lib().s2svc_interp_nearest_rows(dt(x), B, Tin, Tout, C, ptr(x), ptr(y), ptr(lens_in), ptr(lens_out), stream()),
+               "interp_nearest_rows")
+    return y
+
+
 def interp_nearest_bwd(dy, Tin, ext_in=None, ext_out=None):
     B, Tout, C = dy.shape
     dx = torch.empty((B, Tin, C), dtype=dy.dtype, device=dy.device)

@@ -86,6 +86,36 @@ def convmod_wgrad_final(ws_w, chunks, C, ks, dw=None, db=None, accumulate=False)
     return dw, db
 
 
+def convmod_infer_supported(C, ks):
+    return bool(_lib.lib().s2svc_convmod_infer_supported(C, ks))
+
+
+def convmod_infer(y2, w, bias, run_mean, run_var, gamma, beta, eps, vlens=None, out=None):
+    """Conformer convolution module core in inference mode, fp32 or bf16, one launch (csrc/convmod_infer.hip):
+    y2 (B,T,2C) -> swish(bn_eval(dwconv(glu(y2)))) (B,T,C) with per-row lengths: frames t >= vlens[b] (B int32, device) are the
+    convolution's zero padding and come out as zero; they are never read.  out: a (B,T,C) tensor to write instead of a new one."""
+    B, T, C2 = y2.shape
+    C = C2 // 2
+    if out is None:
+        out = torch.empty((B, T, C), dtype=y2.dtype, device=y2.device)
+    _lib.check(_lib.lib().s2svc_convmod_infer(dt(y2), B, T, C, w.shape[-1], ptr(y2), ptr(w), ptr(bias), ptr(run_mean), ptr(run_var),
+                                              ptr(gamma), ptr(beta), eps, ptr(out), ptr(vlens), stream()), "convmod_infer")
+    return out
+
+
+def durations_finalize(d, text_lens_i32, dmax):
+    """Predicted durations d (B,Tx) fp32 or int64 -> (d_outs (B,Tx) in d's dtype: clamped at dmax, 0 beyond text_lens[b];
+    ds (B,Tx) fp32: d_outs with an all-zero row set to 1 in its valid entries; total (B) int32: the row sums of ds)."""
+    assert d.dtype in (torch.float32, torch.int64) and d.is_contiguous()
+    B, Tx = d.shape
+    d_outs = torch.empty_like(d)
+    ds = torch.empty((B, Tx), dtype=torch.float32, device=d.device)
+    total = torch.empty((B,), dtype=torch.int32, device=d.device)
+    _lib.check(_lib.lib().s2svc_durations_finalize(1 if d.dtype == torch.int64 else 0, B, Tx, ptr(d), ptr(text_lens_i32), float(dmax),
+                                                   ptr(d_outs), ptr(ds), ptr(total), stream()), "durations_finalize")
+    return d_outs, ds, total
+
+
 def pairwise_l2_logsoftmax(feats, text, text_lens_i32):
     B, Tf, A = feats.shape
     Tx = text.shape[1]
