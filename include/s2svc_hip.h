@@ -552,6 +552,20 @@ int s2svc_attn_fused_bwd(int B, int H, int T1, int T2, int dk, const void* q, in
                          uint64_t seed_off, void* dq, int64_t lddq, int64_t dqbs, void* dk_out, int64_t lddk, int64_t dkbs, void* dv,
                          int64_t lddv, int64_t dvbs, void* stream);
 
+/* The same backward with the out-projection's data gradient as its prologue (attn_proj_bwd_kernel): */
+/* instead of dout = dctx it reads dy (B, T1, D), the gradient of the out-projection's OUTPUT    */
+/* (element [b*ybs + t*ldy + n]), and wot = W_o^T (D_in, D_out) bf16, row pitch ldw (the          */
+/* optimiser's transposed shadow); a (b, h) workgroup computes its head's dctx columns with the   */
+/* GEMM's instruction, K order and rounding, and dctx is never written.  D = H*dk <= 512.         */
+/* s2svc_attn_proj_supported: nproj = 0 asks for this backward; nproj = 1 / 3 (Q / Q|K|V folded   */
+/* into the forward) are reserved and reported unsupported.                                       */
+int s2svc_attn_proj_supported(int dtype, int T1, int T2, int dk, int D, int nproj);
+int s2svc_attn_proj_bwd(int B, int H, int T1, int T2, int dk, const void* q, int64_t ldq, int64_t qbs, const void* k, int64_t ldk,
+                        int64_t kbs, const void* v, int64_t ldv, int64_t vbs, const void* dy, int64_t ldy, int64_t ybs,
+                        const void* wot, int64_t ldw, const void* attn, const void* dattn, int ld, float scale, float drop_p,
+                        const uint64_t* seed_base, uint64_t seed_off, void* dq, int64_t lddq, int64_t dqbs, void* dk_out,
+                        int64_t lddk, int64_t dkbs, void* dv, int64_t lddv, int64_t dvbs, void* stream);
+
 /* ========================================================================================== */
 /* Relative-position self-attention without the (B, H, T, 2T-1) position term in memory        */
 /* (csrc/relattn.hip): bf16, T <= 256, d_k % 32 == 0, the "new" rel_shift (pos has 2T-1 rows). */

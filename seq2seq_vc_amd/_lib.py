@@ -243,6 +243,10 @@ _SIGS = {
     "s2svc_attn_fused_bwd": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                              c_i64, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp, c_u64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
                              c_i64, c_vp],
+    "s2svc_attn_proj_supported": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32],
+    "s2svc_attn_proj_bwd": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64,
+                            c_i64, c_vp, c_i64, c_vp, c_vp, c_i32, c_f32, c_f32, c_vp, c_u64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64,
+                            c_vp, c_i64, c_i64, c_vp],
     "s2svc_relattn_supported": [c_i32, c_i32, c_i32, c_i32],
     "s2svc_relattn_fwd": [c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, c_i32, c_vp, c_vp, c_vp, c_f32,
                           c_f32, c_vp, c_u64, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp],

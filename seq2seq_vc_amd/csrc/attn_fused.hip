@@ -11,6 +11,8 @@
 // Roundings to bf16: the stored map; its dropped copy bf16(stored map * keep), which is what meets V (and, in the backward, dO);
 // dS before the dQ / dK products; the stored outputs.  Everything else is fp32.
 // Dropout masks are functions of (seed, element index in the attention map) -- the backward regenerates them.
+// attn_proj_bwd_kernel is the backward with the out-projection's data gradient as its prologue (dctx computed per head from dY and W_o^T,
+// never stored): see the comment above it.
 #include "common.h"
 #include "../../include/s2svc_hip.h"
 
@@ -213,45 +215,14 @@ __global__ __launch_bounds__(256) void attn_fused_fwd_kernel(int H, int T1, int 
   }
 }
 
-template <int DK>
-__global__ __launch_bounds__(256) void attn_fused_bwd_kernel(int H, int T1, int T2, const bf16_t* __restrict__ q, int64_t ldq, int64_t qbs,
-                                                             const bf16_t* __restrict__ k, int64_t ldk, int64_t kbs,
-                                                             const bf16_t* __restrict__ v, int64_t ldv, int64_t vbs,
-                                                             const bf16_t* __restrict__ dout, int64_t ldo, int64_t obs,
-                                                             const bf16_t* __restrict__ attn, const bf16_t* __restrict__ dattn, int ld,
-                                                             float scale, float p, const uint64_t* seed_base, uint64_t seed_off,
-                                                             bf16_t* __restrict__ dq, int64_t lddq, int64_t dqbs,
-                                                             bf16_t* __restrict__ dkk, int64_t lddk, int64_t dkbs,
-                                                             bf16_t* __restrict__ dv, int64_t lddv, int64_t dvbs) {
-  constexpr int KP = DK + 8;
-  __shared__ __attribute__((aligned(16))) bf16_t Vs[64 * KP];     // V rows      (B operand of dP = dO V^T)
-  __shared__ __attribute__((aligned(16))) bf16_t Kt[DK * TP];     // K^T         (B operand of dQ = dS K)
-  __shared__ __attribute__((aligned(16))) bf16_t Qt[DK * TP];     // Q^T         (B operand of dK = dS^T Q)
-  __shared__ __attribute__((aligned(16))) bf16_t dOt[DK * TP];    // dO^T        (B operand of dV = P^T dO)
-  __shared__ __attribute__((aligned(16))) bf16_t dSt[64 * TP];    // dS^T        (A operand of dK)
-  __shared__ __attribute__((aligned(16))) bf16_t Pt[64 * TP];     // Pdrop^T     (A operand of dV)
-  __shared__ __attribute__((aligned(16))) bf16_t dSw[4][16 * TP]; // dS rows of each wave (A operand of dQ)
-  const int b = blockIdx.x / H, h = blockIdx.x % H;
+// The lane's 16 attention-map / map-gradient elements of the softmax backward ([jn][r]: row wave*16 + lg*4 + r, column jn*16 + lr)
+__device__ __forceinline__ void load_map_rows(const bf16_t* __restrict__ attn, const bf16_t* __restrict__ dattn, int bh, int T1, int T2, int ld,
+                                              u32x4_t (&praw)[4], u32x4_t (&graw)[4]) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
-  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
-  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  // every global read of the kernel is issued here, before the first LDS store (see load_rows): the four operand tiles, this
-  // wave's dO fragments, and the lane's 16 attention-map / map-gradient elements of the softmax backward
-  uint4 rv[DK / 32], rk[DK / 32], rq[DK / 32], rdo[DK / 32];
-  load_rows<DK>(v + (int64_t)b * vbs + h * DK, ldv, T2, rv);
-  load_rows_t<DK>(k + (int64_t)b * kbs + h * DK, ldk, T2, rk);
-  load_rows_t<DK>(q + (int64_t)b * qbs + h * DK, ldq, T1, rq);
-  load_rows_t<DK>(dout + (int64_t)b * obs + h * DK, ldo, T1, rdo);
-  const int qi = wave * 16 + lr;
-  bf16x8_t da[DK / 32];
-#pragma unroll
-  for (int ks = 0; ks < DK / 32; ++ks)
-    da[ks] = qi < T1 ? *reinterpret_cast<const bf16x8_t*>(dout + (int64_t)b * obs + (int64_t)qi * ldo + h * DK + ks * 32 + lg * 8) : zero8();
-  u32x4_t praw[4], graw[4];            // [jn][r]
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = wave * 16 + lg * 4 + r;
-    const int64_t arow = ((int64_t)(b * H + h) * T1 + i) * ld;
+    const int64_t arow = ((int64_t)bh * T1 + i) * ld;
 #pragma unroll
     for (int jn = 0; jn < 4; ++jn) {
       const int j = jn * 16 + lr;
@@ -260,11 +231,21 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(int H, int T1, int 
       graw[jn][r] = (dattn && in) ? dattn[arow + j] : 0u;
     }
   }
-  put_rows<DK>(rv, Vs);
-  put_rows_t<DK>(rk, Kt);
-  put_rows_t<DK>(rq, Qt);
-  put_rows_t<DK>(rdo, dOt);
-  __syncthreads();
+}
+
+// The backward pass from the staged operands on: Vs / Kt / Qt / dOt hold V, K^T, Q^T, dO^T of this (utterance, head), `da` this wave's dO
+// fragments; the caller has passed the barrier behind the staging.  Shared by attn_fused_bwd_kernel (dO read from memory) and
+// attn_proj_bwd_kernel (dO computed from the out-projection's output gradient): ONE copy of the arithmetic.
+template <int DK>
+__device__ __forceinline__ void attn_bwd_core(int b, int h, int H, int T1, int T2, int ld, float scale, float p, uint64_t seed,
+                                              const bf16x8_t (&da)[DK / 32], const u32x4_t (&praw)[4], const u32x4_t (&graw)[4],
+                                              bf16_t* Vs, const bf16_t* Kt, const bf16_t* Qt, const bf16_t* dOt, bf16_t* dSt, bf16_t* Pt,
+                                              bf16_t* dSw, bf16_t* __restrict__ dq, int64_t lddq, int64_t dqbs,
+                                              bf16_t* __restrict__ dkk, int64_t lddk, int64_t dkbs, bf16_t* __restrict__ dv, int64_t lddv,
+                                              int64_t dvbs) {
+  constexpr int KP = DK + 8;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   // dP = dO . V^T
   f32x4_t dp[4];
 #pragma unroll
@@ -277,7 +258,7 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(int H, int T1, int 
     }
   }
   // dS = P * (dP*mask + dattn - rowdot) * scale ; Pdrop = P * mask      (accumulator layout: row lg*4+r, column jn*16+lr)
-  bf16_t* dsw = dSw[wave];
+  bf16_t* dsw = dSw + wave * 16 * TP;
 #pragma unroll 1
   for (int r = 0; r < 4; ++r) {
     const int il = lg * 4 + r, i = wave * 16 + il;
@@ -331,6 +312,171 @@ __global__ __launch_bounds__(256) void attn_fused_bwd_kernel(int H, int T1, int 
   }
 }
 
+template <int DK>
+__global__ __launch_bounds__(256) void attn_fused_bwd_kernel(int H, int T1, int T2, const bf16_t* __restrict__ q, int64_t ldq, int64_t qbs,
+                                                             const bf16_t* __restrict__ k, int64_t ldk, int64_t kbs,
+                                                             const bf16_t* __restrict__ v, int64_t ldv, int64_t vbs,
+                                                             const bf16_t* __restrict__ dout, int64_t ldo, int64_t obs,
+                                                             const bf16_t* __restrict__ attn, const bf16_t* __restrict__ dattn, int ld,
+                                                             float scale, float p, const uint64_t* seed_base, uint64_t seed_off,
+                                                             bf16_t* __restrict__ dq, int64_t lddq, int64_t dqbs,
+                                                             bf16_t* __restrict__ dkk, int64_t lddk, int64_t dkbs,
+                                                             bf16_t* __restrict__ dv, int64_t lddv, int64_t dvbs) {
+  constexpr int KP = DK + 8;
+  __shared__ __attribute__((aligned(16))) bf16_t Vs[64 * KP];     // V rows      (B operand of dP = dO V^T)
+  __shared__ __attribute__((aligned(16))) bf16_t Kt[DK * TP];     // K^T         (B operand of dQ = dS K)
+  __shared__ __attribute__((aligned(16))) bf16_t Qt[DK * TP];     // Q^T         (B operand of dK = dS^T Q)
+  __shared__ __attribute__((aligned(16))) bf16_t dOt[DK * TP];    // dO^T        (B operand of dV = P^T dO)
+  __shared__ __attribute__((aligned(16))) bf16_t dSt[64 * TP];    // dS^T        (A operand of dK)
+  __shared__ __attribute__((aligned(16))) bf16_t Pt[64 * TP];     // Pdrop^T     (A operand of dV)
+  __shared__ __attribute__((aligned(16))) bf16_t dSw[4 * 16 * TP]; // dS rows of each wave (A operand of dQ)
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
+  // every global read of the kernel is issued here, before the first LDS store (see load_rows): the four operand tiles, this
+  // wave's dO fragments, and the lane's 16 attention-map / map-gradient elements of the softmax backward
+  uint4 rv[DK / 32], rk[DK / 32], rq[DK / 32], rdo[DK / 32];
+  load_rows<DK>(v + (int64_t)b * vbs + h * DK, ldv, T2, rv);
+  load_rows_t<DK>(k + (int64_t)b * kbs + h * DK, ldk, T2, rk);
+  load_rows_t<DK>(q + (int64_t)b * qbs + h * DK, ldq, T1, rq);
+  load_rows_t<DK>(dout + (int64_t)b * obs + h * DK, ldo, T1, rdo);
+  const int qi = wave * 16 + lr;
+  bf16x8_t da[DK / 32];
+#pragma unroll
+  for (int ks = 0; ks < DK / 32; ++ks)
+    da[ks] = qi < T1 ? *reinterpret_cast<const bf16x8_t*>(dout + (int64_t)b * obs + (int64_t)qi * ldo + h * DK + ks * 32 + lg * 8) : zero8();
+  u32x4_t praw[4], graw[4];            // [jn][r]
+  load_map_rows(attn, dattn, b * H + h, T1, T2, ld, praw, graw);
+  put_rows<DK>(rv, Vs);
+  put_rows_t<DK>(rk, Kt);
+  put_rows_t<DK>(rq, Qt);
+  put_rows_t<DK>(rdo, dOt);
+  __syncthreads();
+  attn_bwd_core<DK>(b, h, H, T1, T2, ld, scale, p, seed, da, praw, graw, Vs, Kt, Qt, dOt, dSt, Pt, dSw, dq, lddq, dqbs, dkk, lddk, dkbs, dv,
+                    lddv, dvbs);
+}
+
+// The backward with the out-projection's DATA GRADIENT folded in: instead of dO (= dctx, what a GEMM launch ahead of attn_fused_bwd
+// computes from the gradient dY of the out-projection's output) the kernel reads dY (B, T1, D) and W_o^T (D_in, D_out), the
+// optimiser's transposed shadow, and computes its own head's columns  dO_h[i, c] = sum_n dY[b, i, n] . W_o[n, h*DK + c]  -- rows of
+// this utterance x the head's DK rows of W_o^T: no other workgroup's data, nothing replicated.  The product runs on the MFMA the
+// GEMM uses, over n in ascending 32-steps with the GEMM's fragment mapping (k = ks*32 + lg*8 ..), one fp32 accumulator per
+// element, one rounding to bf16: the values the GEMM stores.  dctx never reaches memory.
+//   * every global load -- the weight slice (DK x D: DK/4 16-byte pieces per lane at most), the wave's 16 dY rows as A fragments
+//     (D/32 per lane), the V / K / Q tiles, the map rows -- is issued before the first LDS store: one memory round trip
+//   * the weight slice is staged in 64-column chunks [chunk][row][TP] over the tiles that are only filled later (the block is
+//     max(tiles, 8 chunks)); a barrier frees it, then V / K^T / Q^T are stored from their registers, dO^T from the accumulators,
+//     and the wave's dO fragments come back through a wave-private tile (the dS^T / Pdrop^T area, written after the next barrier)
+//   * NKC = number of 64-column chunks, compiled for 2 / 4 / 6 / 8 (D <= 128 / 256 / 384 / 512): the K loop is unrolled (its A
+//     fragments are registers) and free of branches -- K steps in [D, 64 NKC) multiply zero fragments with zero weights
+constexpr int PROJ_MAX_D = 512;
+template <int DK, int NKC> constexpr int attn_proj_bwd_lds() {
+  constexpr int tiles = 64 * (DK + 8) + 3 * DK * TP + 2 * 64 * TP + 4 * 16 * TP, wst = NKC * DK * TP;
+  return tiles > wst ? tiles : wst;
+}
+
+template <int DK, int NKC>
+__global__ __launch_bounds__(256) void attn_proj_bwd_kernel(int H, int T1, int T2, const bf16_t* __restrict__ q, int64_t ldq, int64_t qbs,
+                                                            const bf16_t* __restrict__ k, int64_t ldk, int64_t kbs,
+                                                            const bf16_t* __restrict__ v, int64_t ldv, int64_t vbs,
+                                                            const bf16_t* __restrict__ dy, int64_t ldy, int64_t ybs,
+                                                            const bf16_t* __restrict__ wot, int64_t ldw,
+                                                            const bf16_t* __restrict__ attn, const bf16_t* __restrict__ dattn, int ld,
+                                                            float scale, float p, const uint64_t* seed_base, uint64_t seed_off,
+                                                            bf16_t* __restrict__ dq, int64_t lddq, int64_t dqbs,
+                                                            bf16_t* __restrict__ dkk, int64_t lddk, int64_t dkbs,
+                                                            bf16_t* __restrict__ dv, int64_t lddv, int64_t dvbs) {
+  constexpr int KP = DK + 8, NKS = 2 * NKC, RPC = DK / 32;          // RPC: 32-row pieces of a chunk = 16-byte pieces per lane and chunk
+  __shared__ __attribute__((aligned(16))) bf16_t smem[attn_proj_bwd_lds<DK, NKC>()];
+  bf16_t* Vs = smem;
+  bf16_t* Kt = Vs + 64 * KP;
+  bf16_t* Qt = Kt + DK * TP;
+  bf16_t* dOt = Qt + DK * TP;
+  bf16_t* dSt = dOt + DK * TP;
+  bf16_t* Pt = dSt + 64 * TP;
+  bf16_t* dSw = Pt + 64 * TP;
+  bf16_t* Ws = smem;                   // the weight slice, until the barrier behind the projection
+  static_assert(64 * KP <= 2 * 64 * TP, "the waves' dO tiles fit the dS^T / Pdrop^T area");
+  const int D = H * DK;                // in (64 (NKC - 2), 64 NKC]
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, lg = lane >> 4;
+  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
+  // ---- every global read.  Weight slice: lane -> row (tid >> 3) + 32 j of the head's DK rows, 16-byte piece tid & 7 of chunk kc
+  uint4 rw[NKC][RPC];
+  const int wrow = threadIdx.x >> 3, wcol = (threadIdx.x & 7) * 8;
+  const bf16_t* wl = wot + ((int64_t)h * DK + wrow) * ldw + wcol;
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+    for (int j = 0; j < RPC; ++j) {
+      rw[kc][j] = make_uint4(0, 0, 0, 0);
+      if (kc < NKC - 2 || kc * 64 + wcol < D) rw[kc][j] = *reinterpret_cast<const uint4*>(wl + (int64_t)(32 * j) * ldw + kc * 64);
+    }
+  const int qi = wave * 16 + lr;
+  bf16x8_t ya[NKS];
+  const bf16_t* yl = dy + (int64_t)b * ybs + (int64_t)qi * ldy + lg * 8;
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks)
+    ya[ks] = (qi < T1 && (ks < NKS - 4 || ks * 32 < D)) ? *reinterpret_cast<const bf16x8_t*>(yl + ks * 32) : zero8();
+  uint4 rv[DK / 32], rk[DK / 32], rq[DK / 32];
+  load_rows<DK>(v + (int64_t)b * vbs + h * DK, ldv, T2, rv);
+  load_rows_t<DK>(k + (int64_t)b * kbs + h * DK, ldk, T2, rk);
+  load_rows_t<DK>(q + (int64_t)b * qbs + h * DK, ldq, T1, rq);
+  u32x4_t praw[4], graw[4];            // [jn][r]
+  load_map_rows(attn, dattn, b * H + h, T1, T2, ld, praw, graw);
+  // ---- dO_h = dY_b . W_o[:, head columns]
+#pragma unroll
+  for (int kc = 0; kc < NKC; ++kc)
+#pragma unroll
+    for (int j = 0; j < RPC; ++j) *reinterpret_cast<uint4*>(Ws + (kc * DK + wrow + 32 * j) * TP + wcol) = rw[kc][j];
+  __syncthreads();
+  f32x4_t o[DK / 16];
+#pragma unroll
+  for (int dn = 0; dn < DK / 16; ++dn) o[dn] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  // (the B fragments of step ks + 1 are read while the MFMAs of step ks run: the scheduling barriers keep the compiler from
+  // folding the reads back into one register quadruple, which serialises every MFMA behind an LDS round trip)
+  bf16x8_t wb[2][DK / 16];
+#pragma unroll
+  for (int dn = 0; dn < DK / 16; ++dn) wb[0][dn] = *reinterpret_cast<const bf16x8_t*>(Ws + (dn * 16 + lr) * TP + lg * 8);
+#pragma unroll
+  for (int ks = 0; ks < NKS; ++ks) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (ks + 1 < NKS) {
+#pragma unroll
+      for (int dn = 0; dn < DK / 16; ++dn)
+        wb[(ks + 1) & 1][dn] =
+            *reinterpret_cast<const bf16x8_t*>(Ws + (((ks + 1) >> 1) * DK + dn * 16 + lr) * TP + ((ks + 1) & 1) * 32 + lg * 8);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int dn = 0; dn < DK / 16; ++dn) o[dn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ya[ks], wb[ks & 1][dn], o[dn], 0, 0, 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave is past its reads of the slice: the tiles take its place
+  put_rows<DK>(rv, Vs);
+  put_rows_t<DK>(rk, Kt);
+  put_rows_t<DK>(rq, Qt);
+  // dO rounded to bf16, as the GEMM stores it (rows past T1 are zero: their A fragments were): transposed into dOt (a lane holds 4
+  // consecutive rows of one column: 8-byte stores), and row-major into the wave's tile, from which its A fragments are read back
+  // (LDS ops of one wavefront execute in order: no barrier)
+  bf16_t* tile = dSt + wave * 16 * KP;
+  bf16x8_t da[DK / 32];
+#pragma unroll
+  for (int dn = 0; dn < DK / 16; ++dn) {
+    const uint32_t lo = f2bf2(o[dn][0], o[dn][1]), hi = f2bf2(o[dn][2], o[dn][3]);
+    *reinterpret_cast<uint2*>(dOt + (dn * 16 + lr) * TP + wave * 16 + lg * 4) = make_uint2(lo, hi);
+    tile[(lg * 4 + 0) * KP + dn * 16 + lr] = (bf16_t)(lo & 0xffffu);
+    tile[(lg * 4 + 1) * KP + dn * 16 + lr] = (bf16_t)(lo >> 16);
+    tile[(lg * 4 + 2) * KP + dn * 16 + lr] = (bf16_t)(hi & 0xffffu);
+    tile[(lg * 4 + 3) * KP + dn * 16 + lr] = (bf16_t)(hi >> 16);
+  }
+#pragma unroll
+  for (int ks = 0; ks < DK / 32; ++ks) da[ks] = *reinterpret_cast<const bf16x8_t*>(tile + lr * KP + ks * 32 + lg * 8);
+  __syncthreads();
+  attn_bwd_core<DK>(b, h, H, T1, T2, ld, scale, p, seed, da, praw, graw, Vs, Kt, Qt, dOt, dSt, Pt, dSw, dq, lddq, dqbs, dkk, lddk, dkbs, dv,
+                    lddv, dvbs);
+}
+
 }  // namespace
 
 extern "C" int s2svc_attn_fused_supported(int dtype, int T1, int T2, int dk) {
@@ -379,5 +525,44 @@ extern "C" int s2svc_attn_fused_bwd(int B, int H, int T1, int T2, int dk, const 
   if (dk == 32) S2S_AF_BWD(32); else if (dk == 64) S2S_AF_BWD(64); else if (dk == 96) S2S_AF_BWD(96); else S2S_AF_BWD(128);
 #undef S2S_AF_BWD
   S2S_CHECK_LAUNCH("attn_fused_bwd_kernel");
+  return 0;
+}
+
+/* the fused backward with the out-projection's data gradient as its prologue (attn_proj_bwd_kernel) */
+extern "C" int s2svc_attn_proj_supported(int dtype, int T1, int T2, int dk, int D, int nproj) {
+  // nproj: projections folded into the FORWARD (1: Q, 3: Q|K|V); 0: the backward with the out-projection's data gradient --
+  // the only fold this library carries
+  return s2svc_attn_fused_supported(dtype, T1, T2, dk) && D >= dk && D % dk == 0 && D % 32 == 0 && D <= PROJ_MAX_D && nproj == 0;
+}
+
+extern "C" int s2svc_attn_proj_bwd(int B, int H, int T1, int T2, int dk, const void* q, int64_t ldq, int64_t qbs, const void* k,
+                                   int64_t ldk, int64_t kbs, const void* v, int64_t ldv, int64_t vbs, const void* dy, int64_t ldy,
+                                   int64_t ybs, const void* wot, int64_t ldw, const void* attn, const void* dattn, int ld, float scale,
+                                   float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* dq, int64_t lddq, int64_t dqbs,
+                                   void* dk_out, int64_t lddk, int64_t dkbs, void* dv, int64_t lddv, int64_t dvbs, void* stream) {
+  S2S_REQUIRE(H >= 1 && s2svc_attn_proj_supported(S2S_BF16, T1, T2, dk, H * dk, 0),
+              "attn_proj_bwd: unsupported shape (bf16, T <= 64, d_k in {32,64,96,128}, D = H d_k <= 512)");
+  S2S_REQUIRE(ld >= T2, "attn_proj_bwd: the map's row pitch ld must be >= T2");
+  S2S_REQUIRE(ldy >= (int64_t)H * dk && ldw >= (int64_t)H * dk, "attn_proj_bwd: rows of dY and W_o^T hold D elements");
+  S2S_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldy % 8 == 0 && ldw % 8 == 0 && qbs % 8 == 0 && kbs % 8 == 0 &&
+              vbs % 8 == 0 && ybs % 8 == 0, "attn_proj_bwd: strides must be multiples of 8 elements");
+  S2S_REQUIRE(((uintptr_t)q) % 16 == 0 && ((uintptr_t)k) % 16 == 0 && ((uintptr_t)v) % 16 == 0 && ((uintptr_t)dy) % 16 == 0 &&
+              ((uintptr_t)wot) % 16 == 0, "attn_proj_bwd: 16-byte aligned q/k/v/dY/W_o^T");
+  if (B == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+#define S2S_AP_BWD(DK, NKC)                                                                                                     \
+  hipLaunchKernelGGL((attn_proj_bwd_kernel<DK, NKC>), dim3(B * H), dim3(256), 0, st, H, T1, T2, (const bf16_t*)q, ldq, qbs,      \
+                     (const bf16_t*)k, ldk, kbs, (const bf16_t*)v, ldv, vbs, (const bf16_t*)dy, ldy, ybs, (const bf16_t*)wot, ldw, \
+                     (const bf16_t*)attn, (const bf16_t*)dattn, ld, scale, drop_p, seed_base, seed_off, (bf16_t*)dq, lddq, dqbs,  \
+                     (bf16_t*)dk_out, lddk, dkbs, (bf16_t*)dv, lddv, dvbs)
+#define S2S_AP_BWD_D(DK)                                                                            \
+  do {                                                                                              \
+    if (H * DK <= 128) S2S_AP_BWD(DK, 2); else if (H * DK <= 256) S2S_AP_BWD(DK, 4);                \
+    else if (H * DK <= 384) S2S_AP_BWD(DK, 6); else S2S_AP_BWD(DK, 8);                              \
+  } while (0)
+  if (dk == 32) S2S_AP_BWD_D(32); else if (dk == 64) S2S_AP_BWD_D(64); else if (dk == 96) S2S_AP_BWD_D(96); else S2S_AP_BWD_D(128);
+#undef S2S_AP_BWD_D
+#undef S2S_AP_BWD
+  S2S_CHECK_LAUNCH("attn_proj_bwd_kernel");
   return 0;
 }

@@ -359,12 +359,25 @@ class MultiHeadedAttention(nn.Module):
         kl = None if klens is None else klens.dev
         f = getattr(self, "_fused", None)   # packed Q/K/V views of the flat parameter buffer (optim.FlatAdam)
         qp = None
+        wo, bo = self.linear_out.weight, self.linear_out.bias
+        packed = f is not None and key is value and (query is not key or "w_qkv" in f)
+        if (kv is not None or packed) and Fn.attn_block_ok(query, (key if kv is None else kv).shape[1], kv, self.h, wo):
+            # short sequences, bf16, training: projection + core + out-projection as one autograd node (its backward folds the
+            # out-projection's data gradient into the core's launch)
+            if kv is None and query is key:
+                r = Fn.attention_block_qkv(query, f["w_qkv"], f["b_qkv"], wo, bo, kl, causal, self.h, self._p(), passthrough)
+            else:
+                if kv is None:
+                    kv = Fn.linear(key, f["w_kv"], f["b_kv"])                           # ONE GEMM, N = 2D
+                r = Fn.attention_block_kv(query, f["w_q"], f["b_q"], kv, wo, bo, kl, causal, self.h, self._p(), passthrough)
+            self.attn = r[1]
+            return (r[0], r[2]) if passthrough else r[0]
         if kv is not None:
             q = Fn.linear(query, f["w_q"], f["b_q"], passthrough=passthrough)
             if passthrough:
                 q, qp = q
             ctx, self.attn = Fn.attention_packed_kv(q, kv, kl, causal, self.h, self._p())
-        elif f is not None and key is value and (query is not key or "w_qkv" in f):
+        elif packed:
             if query is key:
                 qkv = Fn.linear(query, f["w_qkv"], f["b_qkv"], passthrough=passthrough)   # ONE GEMM, N = 3D
                 if passthrough:
@@ -382,7 +395,7 @@ class MultiHeadedAttention(nn.Module):
             v = Fn.linear(value, self.linear_v.weight, self.linear_v.bias)
             ctx, self.attn = Fn.attention_core(q, k, v, kl, causal, self.h, self._p())
             qp = query
-        out = Fn.linear(ctx, self.linear_out.weight, self.linear_out.bias)
+        out = Fn.linear(ctx, wo, bo)
         return (out, qp) if passthrough else out
 
 

@@ -494,42 +494,48 @@ class _Linear(Function):
             return g_pass, None, None, None, None
         x2, w, y = ctx.saved_tensors
         weight, bias = ctx.params
-        M, Kd = x2.shape
-        N = w.shape[0]
-        dtype = x2.dtype
-        dy2 = _c(dy).view(M, N)
-        if ctx.act:
-            dy2 = K.act_dropout_bwd(dy2, y, act=ctx.act)
-        ldy, zp, dy_rows = N, False, dy2
-        if dtype == torch.float32 and N % 4 and dy2.is_cuda:
-            # rows of N fp32 values with N % 4 != 0 (the 29 spline parameters of a ConvFlow) keep both gradient GEMMs on the
-            # element-wise fallback kernel (19 + 37 us per flow): a zero-padded copy with rows of a whole number of 16-byte vectors
-            # puts them on the vectorised kernels (the pad columns contribute zeros to the reductions and are never stored)
-            ldy, zp = (N + 3) // 4 * 4, True
-            dy2 = K.pad_cols(dy2, ldy)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty((M, Kd), dtype=dtype, device=dy.device)
-            res = _c(g_pass).view(M, Kd).to(dtype) if g_pass is not None else None
-            K.gemm(K.operand(dy2, ldy, zero_padded=zp), _dgrad_operand(weight, w, N, Kd, dtype), M, Kd, N, dx, in_dtype=dtype, res=res)
-            dx = dx.view(ctx.xshape)
-        dw = db = None
-        if weight.requires_grad:
-            tile, sk = K.plan_gemm(N, Kd, M, dtype=dtype)
-            rs, racc, db = _bias_sink(bias, N)     # bias gradient = row sums of dY^T, fused into the wgrad GEMM
+        dx, dw, db = _linear_bwd(x2, w, y, ctx.act, weight, bias, ctx.has_bias, dy, g_pass, ctx.needs_input_grad[0])
+        return (None if dx is None else dx.view(ctx.xshape)), dw, db, None, None
 
-            def wr(out, acc):
-                K.gemm(K.operand(dy2, ldy, layout=K.RC, zero_padded=zp), K.operand(x2, Kd, layout=K.RC), N, Kd, M, out, in_dtype=dtype,
-                       splitk=sk, tile=tile, accumulate=acc, a_rowsum=rs, a_rowsum_accumulate=racc)
-            if _slotted(weight, bias if ctx.has_bias else None):
-                _side_run(lambda: _emit_wgrad(weight, (N, Kd), wr), keep=(dy2, x2))
-            else:
-                dw = _emit_wgrad(weight, (N, Kd), wr)
-                if dw is not None:
-                    dw = dw.view(weight.shape)  # 1x1 Conv1d weights (N, K, 1) are accepted as Linear weights
-        elif ctx.has_bias and bias.requires_grad:
-            db, _ = _reduce_to(bias, None, 0, dy_rows)
-        return dx, dw, db, None, None
+
+def _linear_bwd(x2, w, y, act, weight, bias, has_bias, dy, g_pass, want_dx):
+    """Backward of y = act(x2 W^T + b) for x2 (M, Kd): -> (dx (M, Kd) = dY W + g_pass, or None without want_dx; dw; db).  The
+    weight / bias gradient goes to the flat-gradient slots on a side stream when the parameters have them (dw = db = None)."""
+    M, Kd = x2.shape
+    N = w.shape[0]
+    dtype = x2.dtype
+    dy2 = _c(dy).view(M, N)
+    if act:
+        dy2 = K.act_dropout_bwd(dy2, y, act=act)
+    ldy, zp, dy_rows = N, False, dy2
+    if dtype == torch.float32 and N % 4 and dy2.is_cuda:
+        # rows of N fp32 values with N % 4 != 0 (the 29 spline parameters of a ConvFlow) keep both gradient GEMMs on the
+        # element-wise fallback kernel (19 + 37 us per flow): a zero-padded copy with rows of a whole number of 16-byte vectors
+        # puts them on the vectorised kernels (the pad columns contribute zeros to the reductions and are never stored)
+        ldy, zp = (N + 3) // 4 * 4, True
+        dy2 = K.pad_cols(dy2, ldy)
+    dx = None
+    if want_dx:
+        dx = torch.empty((M, Kd), dtype=dtype, device=dy.device)
+        res = _c(g_pass).view(M, Kd).to(dtype) if g_pass is not None else None
+        K.gemm(K.operand(dy2, ldy, zero_padded=zp), _dgrad_operand(weight, w, N, Kd, dtype), M, Kd, N, dx, in_dtype=dtype, res=res)
+    dw = db = None
+    if weight.requires_grad:
+        tile, sk = K.plan_gemm(N, Kd, M, dtype=dtype)
+        rs, racc, db = _bias_sink(bias, N)     # bias gradient = row sums of dY^T, fused into the wgrad GEMM
+
+        def wr(out, acc):
+            K.gemm(K.operand(dy2, ldy, layout=K.RC, zero_padded=zp), K.operand(x2, Kd, layout=K.RC), N, Kd, M, out, in_dtype=dtype,
+                   splitk=sk, tile=tile, accumulate=acc, a_rowsum=rs, a_rowsum_accumulate=racc)
+        if _slotted(weight, bias if has_bias else None):
+            _side_run(lambda: _emit_wgrad(weight, (N, Kd), wr), keep=(dy2, x2))
+        else:
+            dw = _emit_wgrad(weight, (N, Kd), wr)
+            if dw is not None:
+                dw = dw.view(weight.shape)  # 1x1 Conv1d weights (N, K, 1) are accepted as Linear weights
+    elif has_bias and bias.requires_grad:
+        db, _ = _reduce_to(bias, None, 0, dy_rows)
+    return dx, dw, db
 
 
 def linear(x, weight, bias=None, act=None, passthrough=False):
@@ -1144,6 +1150,139 @@ def attention_packed_qkv(qkv, klen, causal, H, p=0.0):
 
 def attention_packed_kv(q, kv, klen, causal, H, p=0.0):
     return _AttnPackedKV.apply(q, kv, klen, causal, H, p)
+
+
+# ------------------------------------------------------------------------------------------------
+# Whole attention blocks of the short-sequence path (bf16, T <= 64): input projection + fused core + out-projection as ONE autograd
+# node.  The values are those of Fn.linear -> attention_packed_* -> Fn.linear; what the node buys is the backward pass: the core's
+# kernel takes the gradient of the out-projection's OUTPUT and computes its own head's columns of dctx = dY W_o in its prologue
+# (KAT.proj_bwd: no workgroup needs another's data, nothing is replicated), so the out-projection's data-gradient GEMM -- one
+# dependent launch per block on the chain -- is gone and dctx is never stored.
+# ------------------------------------------------------------------------------------------------
+def attn_block_ok(query, T2, kv, H, w_o):
+    """The one-node blocks run where the fused short-sequence kernels do and the optimiser keeps W_o^T (FlatAdam's `_s2s_bf16_t`);
+    training only (decode / eval keep the separate nodes)."""
+    if not (torch.is_grad_enabled() and query.dim() == 3 and getattr(w_o, "_s2s_bf16_t", None) is not None):
+        return False
+    D = query.shape[-1]
+    if not KAT.proj_bwd_supported(query.dtype, query.shape[1], T2, D // H, D) or D % 8:
+        return False
+    return kv is None or (kv.dtype == query.dtype and kv.stride(-1) == 1 and KAT.view_ok(kv[..., :D]) and KAT.view_ok(kv[..., D:]))
+
+
+def _block_project(x, weight, bias):
+    """x (B, T, D) -> (x2, the compute-dtype weight, x W^T + b as (B, T, N)): the forward of Fn.linear."""
+    dtype = x.dtype
+    x2 = _c(x).view(-1, x.shape[-1])
+    M, Kd = x2.shape
+    N = weight.shape[0]
+    w = _wcast(weight, dtype)
+    y = torch.empty((M, N), dtype=dtype, device=x.device)
+    K.gemm(K.operand(x2, Kd), K.operand(w, Kd), M, N, Kd, y, in_dtype=dtype, bias=bias)
+    return x2, w, y.view(*x.shape[:-1], N)
+
+
+def _block_core_bwd(ctx, dy, dattn, attn, cv, wo, q, k, v, outs):
+    """Out-projection and core of a block, backward: W_o's weight / bias gradient as _Linear queues it, then dq | dk | dv into
+    `outs` -- from dy with the data gradient folded into the core's launch, or through the separate GEMM where that is switched
+    off or does not apply.  -> (dw_o, db_o)."""
+    H, scale, p, seed, D = ctx.meta
+    w_o, b_o = ctx.out_params
+    if dy is None:                     # only the attention map was used
+        _attn_common_bwd(None, dattn, attn, None, q, k, v, H, scale, p, seed, outs=outs)
+        return None, None
+    dy = _c(dy)
+    wot = getattr(w_o, "_s2s_bf16_t", None)
+    # (B T1 > 64: the rows at which the separate GEMM runs its tile kernels, whose K order the prologue repeats -- the same bits;
+    # below, the skinny kernel sums K in four quarters)
+    fold = (wot is not None and dy.shape[0] * dy.shape[1] > 64 and all(t.stride(-1) == 1 for t in outs)
+            and KAT.proj_bwd_ok(q, k, v, dy, wot, H))
+    dctx, dwo, dbo = _linear_bwd(cv.view(-1, D), wo, None, None, w_o, b_o, b_o is not None, dy, None, not fold)
+    if fold:
+        KAT.proj_bwd(q, k, v, dy, wot, attn, _pad_like(dattn, attn), H, scale, p, seed, *outs)
+    else:
+        _attn_common_bwd(dctx.view(cv.shape), dattn, attn, None, q, k, v, H, scale, p, seed, outs=outs)
+    return dwo, dbo
+
+
+class _AttnBlockQKV(Function):
+    """Self-attention block on the packed (3D, D) projection."""
+
+    @staticmethod
+    def forward(ctx, x, w_qkv, b_qkv, w_o, b_o, klen, causal, H, p, passthrough):
+        D = x.shape[-1]
+        x2, wi, qkv = _block_project(x, w_qkv, b_qkv)
+        q, k, v = qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:]
+        cv, attn, pdrop, scale, seed = _attn_fwd_views(q, k, v, klen, causal, H, p)
+        assert pdrop is _FUSED
+        _, wo, y = _block_project(cv, w_o, b_o)
+        ctx.meta = (H, scale, p, seed, D)
+        ctx.in_params, ctx.out_params, ctx.xshape = (w_qkv, b_qkv), (w_o, b_o), x.shape
+        ctx.save_for_backward(x2, wi, qkv, attn, cv, wo)
+        ctx.set_materialize_grads(False)
+        if passthrough:
+            return y, _user_attn(attn, k.shape[1]), x.view_as(x)
+        return y, _user_attn(attn, k.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy, dattn, g_pass=None):
+        if dy is None and dattn is None:
+            return (g_pass,) + (None,) * 9
+        x2, wi, qkv, attn, cv, wo = ctx.saved_tensors
+        D = ctx.meta[4]
+        dqkv = torch.empty_like(qkv)
+        dwo, dbo = _block_core_bwd(ctx, dy, dattn, attn, cv, wo, qkv[..., :D], qkv[..., D:2 * D], qkv[..., 2 * D:],
+                                   (dqkv[..., :D], dqkv[..., D:2 * D], dqkv[..., 2 * D:]))
+        w_in, b_in = ctx.in_params
+        dx, dw, db = _linear_bwd(x2, wi, None, None, w_in, b_in, b_in is not None, dqkv, g_pass, ctx.needs_input_grad[0])
+        return (None if dx is None else dx.view(ctx.xshape)), dw, db, dwo, dbo, None, None, None, None, None
+
+
+class _AttnBlockKV(Function):
+    """Source-attention block: the Q projection of x, the packed K|V projection `kv` (B, T2, 2D) of the memory computed by the caller
+    (used in place: a column block of the decoder's batched projection, its gradient written into the block's _GradSink)."""
+
+    @staticmethod
+    def forward(ctx, x, w_q, b_q, kv, w_o, b_o, klen, causal, H, p, passthrough):
+        D = x.shape[-1]
+        x2, wi, q = _block_project(x, w_q, b_q)
+        k, v = kv[..., :D], kv[..., D:]
+        cv, attn, pdrop, scale, seed = _attn_fwd_views(q, k, v, klen, causal, H, p)
+        assert pdrop is _FUSED
+        _, wo, y = _block_project(cv, w_o, b_o)
+        ctx.meta = (H, scale, p, seed, D)
+        ctx.in_params, ctx.out_params, ctx.xshape = (w_q, b_q), (w_o, b_o), x.shape
+        ctx.gsink = getattr(kv, "_s2s_gsink", None)
+        ctx.save_for_backward(x2, wi, q, kv, attn, cv, wo)
+        ctx.set_materialize_grads(False)
+        if passthrough:
+            return y, _user_attn(attn, k.shape[1]), x.view_as(x)
+        return y, _user_attn(attn, k.shape[1])
+
+    @staticmethod
+    def backward(ctx, dy, dattn, g_pass=None):
+        if dy is None and dattn is None:
+            return (g_pass,) + (None,) * 10
+        x2, wi, q, kv, attn, cv, wo = ctx.saved_tensors
+        D = ctx.meta[4]
+        dq = torch.empty_like(q)
+        if ctx.gsink is not None and dy is not None:
+            dkv = ctx.gsink[0].part(ctx.gsink[1])       # this block of the packed gradient, written where split_cols wants it
+        else:
+            dkv = torch.empty(kv.shape, dtype=kv.dtype, device=kv.device)
+        dwo, dbo = _block_core_bwd(ctx, dy, dattn, attn, cv, wo, q, kv[..., :D], kv[..., D:], (dq, dkv[..., :D], dkv[..., D:]))
+        w_in, b_in = ctx.in_params
+        dx, dw, db = _linear_bwd(x2, wi, None, None, w_in, b_in, b_in is not None, dq, g_pass, ctx.needs_input_grad[0])
+        return (None if dx is None else dx.view(ctx.xshape)), dw, db, dkv, dwo, dbo, None, None, None, None, None
+
+
+def attention_block_qkv(x, w_qkv, b_qkv, w_o, b_o, klen, causal, H, p=0.0, passthrough=False):
+    """(out, attn[, alias of x]): see _AttnBlockQKV; the caller checks attn_block_ok."""
+    return _AttnBlockQKV.apply(x, w_qkv, b_qkv, w_o, b_o, klen, causal, H, p, passthrough)
+
+
+def attention_block_kv(x, w_q, b_q, kv, w_o, b_o, klen, causal, H, p=0.0, passthrough=False):
+    return _AttnBlockKV.apply(x, w_q, b_q, kv, w_o, b_o, klen, causal, H, p, passthrough)
 
 
 class _AttnCore(Function):

@@ -57,6 +57,43 @@ def fused_bwd(q, k, v, dout, attn, dattn, H, scale, p, seed, dq, dk_out, dv):
 
 
 # ----------------------------------------------------------------------------------------------
+# the fused backward with the out-projection's data gradient as its prologue (attn_proj_bwd_kernel)
+# ----------------------------------------------------------------------------------------------
+# S2SVC_NO_ATTN_PROJ (the switch: A/B against the separate launches): "1" = every fold off, "bwd" = the backward fold off;
+# "fwd" names the forward folds (Q / Q|K|V projection ahead of the fused forward), of which this build carries none
+_PROJ_OFF = {"0": set(), "1": {"fwd", "bwd"}, "fwd": {"fwd"}, "bwd": {"bwd"}}[os.environ.get("S2SVC_NO_ATTN_PROJ", "0")]
+
+
+def proj_bwd_supported(dtype, T1, T2, dk, D):
+    """Shape-level: can the fused backward take dY and W_o^T instead of dctx?"""
+    if _DISABLED or "bwd" in _PROJ_OFF or dtype != torch.bfloat16:
+        return False
+    return bool(_lib.lib().s2svc_attn_proj_supported(_DT[dtype], T1, T2, dk, D, 0))
+
+
+def proj_bwd_ok(q, k, v, dy, wot, H):
+    D = q.shape[-1]
+    return (proj_bwd_supported(q.dtype, q.shape[1], k.shape[1], D // H, D) and _strided_ok(q) and _strided_ok(k) and _strided_ok(v)
+            and dy.dtype == q.dtype and _strided_ok(dy) and wot.dtype == q.dtype and tuple(wot.shape) == (D, D) and wot.stride(1) == 1
+            and wot.stride(0) % 8 == 0 and wot.data_ptr() % 16 == 0)
+
+
+def proj_bwd(q, k, v, dy, wot, attn, dattn, H, scale, p, seed, dq, dk_out, dv):
+    """fused_bwd with dctx = dy . W_o computed per head inside the launch: dy (B,T1,D) is the gradient of the out-projection's
+    output, wot = W_o^T (D_in, D_out).  Writes dq / dk / dv (views with last dim contiguous); dctx is never stored."""
+    B, T1, D = q.shape
+    T2 = k.shape[1]
+    for t in (dy, dq, dk_out, dv):
+        if t.stride(2) != 1:
+            raise ValueError("fused attention backward: last dim of gradients must be contiguous")
+    _lib.check(_lib.lib().s2svc_attn_proj_bwd(B, H, T1, T2, D // H, ptr(q), q.stride(1), q.stride(0), ptr(k), k.stride(1), k.stride(0),
+                                              ptr(v), v.stride(1), v.stride(0), ptr(dy), dy.stride(1), dy.stride(0), ptr(wot),
+                                              wot.stride(0), ptr(attn), ptr(dattn), attn.shape[-1], scale, p, seed[0], seed[1], ptr(dq),
+                                              dq.stride(1), dq.stride(0), ptr(dk_out), dk_out.stride(1), dk_out.stride(0), ptr(dv),
+                                              dv.stride(1), dv.stride(0), stream()), "attn_proj_bwd")
+
+
+# ----------------------------------------------------------------------------------------------
 # attention map of plain attention in one launch, T2 <= 512 (csrc/attn_map.hip)
 # ----------------------------------------------------------------------------------------------
 _MAP_DISABLED = os.environ.get("S2SVC_NO_ATTNMAP", "0") == "1"       # (the switch: A/B against scores GEMM + softmax kernel)
