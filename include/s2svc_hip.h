@@ -368,6 +368,29 @@ int s2svc_derived_refresh_plan(const s2svc_derived_job* jobs /* host */, int n, 
    pre_postnets.py:108-165, alignments.py:28-60 call sites).  A * (B + 1) * 4 bytes must fit 64 KB. */
 int s2svc_permute_inner(int n, int A, int B, const float* src, float* dst, int accumulate, void* stream);
 int s2svc_rowscale(int dtype, int64_t rows, int D, const void* x, const float* s, void* out, void* stream);
+/* Weight gradients of 'same'-padded stride-1 Conv1d layers without bias, several layers in ONE launch (csrc/conv1d_wgrad.hip; replaces
+   the split-K GEMM + reduction + permutation of autograd's conv backward at the pre_postnets.py:108-165 call sites):
+     dw[o][i][j] += sum_{b,t} dy[b,t,o] * x[b, t + j - (ks-1)/2, i],   taps outside [0, T) of the same utterance count as zero.
+   dy (B*T, Cout) and x (B*T, Cin) are row-major bf16, 16-byte aligned; dw is fp32 in the parameter's (Cout, Cin, ks) layout and is ADDED
+   to.  Supported: dtype 1 (bf16), ks = 5, Cin and Cout multiples of 16.  A unit is (item, 64 output channels, 64 input channels, all
+   taps) and sums all B*T rows in ascending order in one accumulator set; workgroups walk the units in order, so the result is bit-identical
+   for every max_workgroups (0 = one workgroup per unit).  Items whose dw ranges overlap go to successive launches, as do items beyond 16.
+   chunk_steps > 0: the frames are summed in runs of chunk_steps 64-frame steps (utterance by utterance, ceil(T / 64) steps each), every
+   run from zero, the runs added in ascending order: with T % 64 == 0 and chunk_steps = ceil(B*T / 64 / splitk) these are the partial
+   sums and the reduction of an s2svc_gemm with that split-K, bit for bit -- as long as that GEMM runs 64-row K tiles on the 16x16x32 bf16
+   MFMA (gemm_glds_kernel with row-contiguous operands) and splitk_reduce adds its partials in ascending order; this entry point
+   promises the formula and the order stated here, not that equality.  0: one run.  Every argument is checked before the first launch. */
+typedef struct s2svc_conv1d_wgrad_item {
+  const void* dy;
+  const void* x;
+  float* dw;
+  int32_t B, T, Cin, Cout, ks;
+  int32_t dtype;
+  int32_t chunk_steps;
+  int32_t reserved_;
+} s2svc_conv1d_wgrad_item;
+int s2svc_conv1d_wgrad_supported(int Cout, int Cin, int ks, int dtype);
+int s2svc_conv1d_wgrad_grouped(const s2svc_conv1d_wgrad_item* items /* host */, int n, int max_workgroups, void* stream);
 
 /* ========================================================================================== */
 /* Convolution helpers                                                                         */

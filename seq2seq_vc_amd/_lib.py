@@ -136,6 +136,11 @@ class ColreduceItem(ctypes.Structure):
                 ("scale", c_f32), ("reserved_", c_i32)]
 
 
+class Conv1dWgradItem(ctypes.Structure):
+    _fields_ = [("dy", c_vp), ("x", c_vp), ("dw", c_vp), ("B", c_i32), ("T", c_i32), ("Cin", c_i32), ("Cout", c_i32), ("ks", c_i32),
+                ("dtype", c_i32), ("chunk_steps", c_i32), ("reserved_", c_i32)]
+
+
 _SIGS = {
     "s2svc_gemm": [ctypes.POINTER(GemmDesc), c_vp],
     "s2svc_gemm_grouped_ok": [c_vp],
@@ -200,6 +205,8 @@ _SIGS = {
     "s2svc_derived_refresh": [c_vp, c_i32, c_vp],
     "s2svc_derived_refresh_plan": [c_vp, c_i32, c_vp, c_vp],
     "s2svc_permute_inner": [c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp],
+    "s2svc_conv1d_wgrad_supported": [c_i32, c_i32, c_i32, c_i32],
+    "s2svc_conv1d_wgrad_grouped": [c_vp, c_i32, c_i32, c_vp],
     "s2svc_gather3": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp],
     "s2svc_mas": [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "s2svc_mas_binloss_bwd": [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],

@@ -179,6 +179,7 @@ class _Side:
     batch = 16
     grouped = []     # weight-gradient GEMM descriptors of the batch being flushed
     grouped_cr = []  # column reductions of the batch being flushed
+    grouped_c1w = [] # Conv1d weight gradients (dy, x, dw) of the batch being flushed
     on_flush = None  # callable(): called on the flushing stream behind every flushed batch (distributed.FlushExchange)
 
 
@@ -262,14 +263,17 @@ def _side_run(fn, keep=(), solo=False):
 def _run_batch(closures):
     """Run a batch of gradient closures on the current stream: their dense weight-gradient GEMMs become ONE grouped launch
     (no split-K, no reduction passes), their column reductions into gradient slots (LayerNorm / BatchNorm / bias vectors)
-    two grouped launches; everything else they launch (conv weight gradients, ...) runs as issued."""
-    with K.record_grouped(_Side.grouped), K.record_colreduce(_Side.grouped_cr):
+    two grouped launches, the eligible Conv1d weight gradients of a FORKED batch (the Postnet's) one launch capped like the grouped
+    GEMMs (csrc/conv1d_wgrad.hip); everything else they launch (other conv weight gradients, ...) runs as issued."""
+    with K.record_grouped(_Side.grouped), K.record_colreduce(_Side.grouped_cr), K.record_conv1d_wgrad(_Side.grouped_c1w):
         for fn in closures:
             fn()
     if _Side.grouped:
         K.flush_grouped(_Side.grouped)
     if _Side.grouped_cr:
         K.flush_colreduce(_Side.grouped_cr)
+    if _Side.grouped_c1w:
+        K.flush_conv1d_wgrad(_Side.grouped_c1w, K.get_wgrad_cap())
 
 
 def _inline_flush(key):
@@ -1521,6 +1525,11 @@ class _Conv1d(Function):
         dw = db = None
         if weight.requires_grad:
             def work():
+                # forked gradient batches (VTN, Transformer-TTS): the batch's eligible layers share ONE capped launch that adds into
+                # the (Cout, Cin, ks) slots (csrc/conv1d_wgrad.hip) instead of split-K GEMM + reduction + permutation per layer
+                if (K.get_wgrad_cap() > 0 and _slotted(weight) and K.conv1d_wgrad_enabled()
+                        and K.conv1d_wgrad_supported(Cout, Cin, ks, dtype, bias) and K.conv1d_wgrad_queue(dy, x, weight._s2s_grad)):
+                    return None, None
                 dwp = torch.empty((Cout, ks * Cin), dtype=torch.float32, device=x.device)
                 rs, racc, dbv = _bias_sink(bias, Cout)
                 tile, sk = K.plan_gemm(Cout, ks * Cin, B * T)

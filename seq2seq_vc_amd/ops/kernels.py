@@ -621,6 +621,108 @@ def flush_grouped(queue):
 
 
 # ----------------------------------------------------------------------------------------------
+# Conv1d weight gradients of a gradient batch (csrc/conv1d_wgrad.hip): while a recorder is active, ops.functional queues
+# (dy, x, dw) triples instead of launching split-K GEMM + reduction + permutation per layer; flush_conv1d_wgrad() runs the
+# queue as ONE capped launch that adds straight into the (Cout, Cin, ks) gradient slots.
+# ----------------------------------------------------------------------------------------------
+_C1W_RECORDER = None        # list of (dy, x, dw) while recording
+
+
+class record_conv1d_wgrad:
+    """with record_conv1d_wgrad(queue): conv1d_wgrad_queue(...) appends to `queue` (list); without one it answers False."""
+
+    def __init__(self, queue):
+        self.queue = queue
+
+    def __enter__(self):
+        global _C1W_RECORDER
+        self.prev, _C1W_RECORDER = _C1W_RECORDER, self.queue
+        return self.queue
+
+    def __exit__(self, *exc):
+        global _C1W_RECORDER
+        _C1W_RECORDER = self.prev
+        return False
+
+
+def conv1d_wgrad_enabled():
+    """S2SVC_NO_CONV1D_WGRAD=1 (read per call): today's launches everywhere."""
+    return os.environ.get("S2SVC_NO_CONV1D_WGRAD", "0") != "1"
+
+
+def conv1d_wgrad_supported(Cout, Cin, ks, dtype, bias=None):
+    """True if s2svc_conv1d_wgrad_grouped takes a layer of this shape (bf16, ks 5, channel counts multiples of 16, no bias: the
+    kernel has no bias gradient)."""
+    if bias is not None or dtype not in _DT:
+        return False
+    return bool(_lib.lib().s2svc_conv1d_wgrad_supported(int(Cout), int(Cin), int(ks), _DT[dtype]))
+
+
+def conv1d_wgrad_queue(dy, x, dw):
+    """Queue dw += conv1d weight gradient of (dy, x) on the active recorder -> True; False (nothing done) without a recorder."""
+    if _C1W_RECORDER is None:
+        return False
+    _C1W_RECORDER.append((dy, x, dw))
+    return True
+
+
+def _c1w_item(dy, x, dw):
+    _need_cuda(dy)
+    if dy.dim() != 3 or x.dim() != 3 or dy.shape[:2] != x.shape[:2] or not dy.is_contiguous() or not x.is_contiguous() or dy.dtype != x.dtype:
+        raise TypeError("conv1d_wgrad: dy (B, T, Cout) and x (B, T, Cin) must be contiguous tensors of one dtype and one (B, T)")
+    (B, T, Cout), Cin = dy.shape, x.shape[2]
+    if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.numel() % (Cout * Cin) or dw.device != dy.device:
+        raise TypeError("conv1d_wgrad: dw must be a contiguous fp32 tensor of Cout * Cin * ks elements on the operands' device")
+    it = _lib.Conv1dWgradItem()
+    it.dy, it.x, it.dw = ptr(dy), ptr(x), ptr(dw)
+    it.B, it.T, it.Cin, it.Cout, it.ks, it.dtype = B, T, Cin, Cout, dw.numel() // (Cout * Cin), dt(dy)
+    it.chunk_steps = conv1d_wgrad_chunk(B, T, Cin, Cout, it.ks)
+    return it
+
+
+def conv1d_wgrad_chunk(B, T, Cin, Cout, ks):
+    """Steps per partial sum for the item: the kernel's 64-frame steps are the K tiles of the split-K GEMM it stands in for whenever
+    T % 64 == 0; it then sums them in the runs that GEMM's split-K plan cuts (plan_gemm, as _Conv1d.backward calls it) and adds the runs in
+    the reduction pass's order -- the gradient keeps the bits of the old launches.  Other T: one run (tiles straddle utterances there).
+    This couples the stand-alone kernel to internals of the launches it replaces, on purpose (a training run must not change its numbers
+    with this change), and only here: the equality holds while plan_gemm's split-K plan, the 64-row K tile and MFMA of gemm_glds_kernel's
+    row-contiguous operands and splitk_reduce's ascending order hold (tests/gpu_conv1d_wgrad_check.py: Rule 3 fails when one drifts).  Should
+    those launches go or change, return 0 here: the kernel then sums in one run and the rule of its check alone holds it."""
+    if T % 64:
+        return 0
+    ktiles = B * T // 64
+    sk = max(1, plan_gemm(Cout, ks * Cin, B * T)[1])
+    return (ktiles + sk - 1) // sk if sk > 1 else 0
+
+
+def conv1d_wgrad_grouped(items, cap=0):
+    """dw[o][i][j] += sum_{b,t} dy[b,t,o] x[b,t+j-pad,i] for every (dy, x, dw) of `items`, on the current stream, in one launch of
+    at most `cap` workgroups (0: one per unit) per <= 16 items; items on the same dw go to successive launches.  The library checks
+    every item before the first launch and refuses what conv1d_wgrad_supported refuses."""
+    pending = [(_c1w_item(*t), t) for t in items]
+    while pending:
+        seen, group, rest = set(), [], []
+        for it, keep in pending:
+            if it.dw in seen:
+                rest.append((it, keep))
+            else:
+                seen.add(it.dw)
+                group.append((it, keep))
+        pending = rest
+        arr = (_lib.Conv1dWgradItem * len(group))(*[g[0] for g in group])
+        if _Audit.on:
+            _audit_write("grouped conv1d weight gradient", *[g[0].dw for g in group])
+        _lib.check(_lib.lib().s2svc_conv1d_wgrad_grouped(ctypes.addressof(arr), len(group), int(cap), stream()), "s2svc_conv1d_wgrad_grouped")
+
+
+def flush_conv1d_wgrad(queue, cap=0):
+    """Launch the queued conv1d weight gradients on the current stream (conv1d_wgrad_grouped).  Empties the queue."""
+    items = list(queue)
+    del queue[:]
+    conv1d_wgrad_grouped(items, cap)
+
+
+# ----------------------------------------------------------------------------------------------
 # norms / reductions
 # ----------------------------------------------------------------------------------------------
 def layernorm_fwd(x, gamma, beta, eps, res=None, p=0.0, seed=(None, 0), need_stats=True, hscale=1.0):
