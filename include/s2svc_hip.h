@@ -835,6 +835,45 @@ int s2svc_hifigan_fold(int mode, int D0, int D1, int k, int u, const float* g, c
                        void* stream);
 
 /* ========================================================================================== */
+/* HiFi-GAN generator, backward with respect to the parameters (csrc/hifigan_bwd.hip).  The    */
+/* same channel-last tensors in `dtype`, no absent rows (training batches are not ragged).     */
+/* Masks are the forward's RAW layer inputs: lrelu'(m, s) = 1 for m > 0, s otherwise.  Every   */
+/* sum runs in an order fixed by the shapes: no atomics, two passes give the same bits.        */
+/* replaces: loss.backward() through urhythmic/vocoder.py:87-106, :195-202                     */
+/* (urhythmic_fine_tune_vocoder.py:191-222).                                                   */
+/* ========================================================================================== */
+/* Operand of the data gradient from the folded fp32 weight w32 (D0, D1, k); w_opT is ZERO-FILLED by the caller.
+   mode 0 Conv1d (O, C, k) -> [c][j*Op + o] = w[o, c, k-1-j], Op = O padded;  mode 1 ConvTranspose1d (C, O, k) ->
+   [c][n*Kp + p*O + o] = w[c, o, p + u*n], Kp = u*O padded (s2svc_hifigan_cin_padded). */
+int s2svc_hifigan_fold_bwd(int mode, int D0, int D1, int k, int u, const float* w32, int op_dtype, void* w_opT, void* stream);
+/* Data gradient of s2svc_hifigan_conv1d: dx (B, T, C_in) = (accumulate ? dx : 0) + scale * (lrelu'(mask_src, slope) * conv(dy, w
+   flipped and transposed) (+ res)); dy (B, T, C_out); mask_src / res (B, T, C_in) or NULL. */
+int s2svc_hifigan_conv1d_dgrad(int dtype, int B, int T, int Cin, int Cout, int k, int dil, const void* dy, const void* w_opT,
+                               const void* mask_src, float slope, const void* res, int accumulate, float scale, void* dx, void* stream);
+/* Data gradient of s2svc_hifigan_tconv1d: dy (B, u*T_in, C_out) is read as the forward's GEMM rows (i, (p, o)) at a flat offset of
+   -pad*C_out elements, zero outside the utterance; dx (B, T_in, C_in) = scale * lrelu'(mask_src, slope) * sum_n dy'[i + n] . op[n]. */
+int s2svc_hifigan_tconv1d_dgrad(int dtype, int B, int Tin, int Cin, int Cout, int k, int u, const void* dy, const void* w_opT,
+                                const void* mask_src, float slope, float scale, void* dx, void* stream);
+/* Weight and bias gradient partials.  kind 0 Conv1d: dy (B, T, C_out), x (B, T, C_in), dil_or_u = dilation; kind 1 ConvTranspose1d:
+   dy (B, u*T, C_out), x (B, T, C_in), dil_or_u = stride.  The rows of an utterance (T, or T + ceil(pad/u)) are cut into chunks of
+   `chunk` frames (a multiple of 32); chunk q of utterance b writes wpart[b*ncpu + q][Na][ntaps][C_in] = sum over its rows of
+   dy'[i][m] * leaky_relu(x, slope)[i + offset(tap)][c] and bpart[b*ncpu + q][Na] = the column sums of dy'; Na = C_out or u*C_out,
+   ntaps = k or ceil(k/u) (<= 12).  A halo crosses a chunk edge inside the utterance and reads zero past the utterance's ends. */
+int s2svc_hifigan_wgrad(int dtype, int kind, int B, int T, int Cin, int Cout, int k, int dil_or_u, int chunk, const void* dy,
+                        const void* x, float slope, float* wpart, float* bpart, void* stream);
+/* Sum of nparts partials in ascending order -> the parameter's layout (D0, D1, k) (modes as s2svc_hifigan_fold; mode 1 drops the
+   slots p + u*n >= k; mode 2 partials are [nparts][k][C] / [nparts]), then the weight-norm backward over dim 0 when g is given:
+   grad_g = sum(dw * v) / ||v||, grad_w (= grad_v) = (g / ||v||) dw - (g sum(dw * v) / ||v||^3) v; g = NULL: grad_w = dw.
+   grad_bias (or NULL) = the summed bias partials. */
+int s2svc_hifigan_wgrad_finish(int mode, int D0, int D1, int k, int u, int nparts, const float* wpart, const float* bpart, const float* g,
+                               const float* v, float* grad_w, float* grad_g, float* grad_bias, void* stream);
+/* Backward of s2svc_hifigan_conv_out with tanh: dpre = dy * (1 - y^2); dx (B, T, C) = scale * lrelu'(x, slope) * the C -> 1 data
+   gradient; wpart [B * ceil(T/chunk)][k][C] and bpart [B * ceil(T/chunk)]: partials per chunk of frames (chunk = 256, the workgroup's
+   share; the caller states it so that both sides size the partials alike).  y, dy (B, T) fp32. */
+int s2svc_hifigan_conv_out_bwd(int dtype, int B, int T, int C, int k, int chunk, const void* x, const float* w, const float* y, const float* dy,
+                               float slope, float scale, void* dx, float* wpart, float* bpart, void* stream);
+
+/* ========================================================================================== */
 /* Griffin-Lim phase reconstruction, fp32 (csrc/griffin_lim.hip): librosa.griffinlim with      */
 /* init="random" as vocoder/griffin_lim.py:53-106 calls it, for a batch with per-row lengths   */
 /* in 2 n_iter + 3 launches.  Buffers: S (B, Tmax, bins) fp32, X / Rprev (B, Tmax, bins)       */

@@ -310,6 +310,12 @@ _SIGS = {
     "s2svc_hifigan_conv_out": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp],
     "s2svc_hifigan_input": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
     "s2svc_hifigan_fold": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp],
+    "s2svc_hifigan_fold_bwd": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp],
+    "s2svc_hifigan_conv1d_dgrad": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_vp, c_i32, c_f32, c_vp, c_vp],
+    "s2svc_hifigan_tconv1d_dgrad": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp],
+    "s2svc_hifigan_wgrad": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp],
+    "s2svc_hifigan_wgrad_finish": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "s2svc_hifigan_conv_out_bwd": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp],
     "s2svc_gl_supported": [c_i32],
     "s2svc_gl_prepare": [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, c_vp,
                          c_vp],

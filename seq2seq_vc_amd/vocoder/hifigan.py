@@ -1,9 +1,14 @@
-"""HiFi-GAN generator on the HIP kernels of csrc/hifigan.hip: mel -> waveform, single and batched, inference only.
+"""HiFi-GAN generator on the HIP kernels of csrc/hifigan.hip: mel -> waveform, single and batched; with `trainable()` also the
+backward pass with respect to its parameters (csrc/hifigan_bwd.hip), for fine-tuning.
 
 Drop-in surface of the reference's `seq2seq_vc/urhythmic/vocoder.py` HifiganGenerator (constructor keywords, defaults and
 `state_dict` keys, with and without weight norm) and of `seq2seq_vc/vocoder/vocoder.py` Vocoder.decode.  Every convolution is one
 launch; activation, residual, the MRF sum / average, tanh and the input transposition / normalisation / cast ride in the kernels'
-prologues and epilogues, so a call of the default configuration is 79 launches (`launch_plan()`).  There is no CPU path."""
+prologues and epilogues, so a call of the default configuration is 79 launches (`launch_plan()`).  There is no CPU path.
+
+Fine-tuning (reference: urhythmic_fine_tune_vocoder.py:191-222): `generator.trainable()` makes forward() return a tensor with a
+grad_fn; one autograd Function takes every parameter as an input, so `.grad`, accumulation, zero_grad and DDP hooks work as on any
+module.  The input never gets a gradient (units / mels are data).  One backward pass is `backward_plan()`."""
 import math
 
 import numpy as np
@@ -16,6 +21,7 @@ from ..ops import kernels_vocoder as KV
 LRELU_SLOPE = 0.1
 POST_SLOPE = 0.01        # vocoder.py:103 applies F.leaky_relu with torch's DEFAULT slope in front of conv_post
 KINDS = ("input", "conv1d", "tconv1d", "conv_out")   # the input launch + the kernel families a call may launch ("fold" runs at load)
+BWD_KINDS = ("conv_out_bwd", "wgrad", "finish", "conv1d_dgrad", "tconv1d_dgrad")    # the launches of one backward pass
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -104,8 +110,26 @@ class ResBlock(nn.Module):
         self.convs2 = nn.ModuleList([mk() for _ in dilation])
 
 
+class _GeneratorFunction(torch.autograd.Function):
+    """forward(x) of a trainable generator as ONE autograd node over all its parameters (x gets no gradient)."""
+
+    @staticmethod
+    def forward(ctx, gen, x, taps, *params):
+        y, state = gen._forward_train(x, taps)
+        ctx.gen, ctx.state = gen, state
+        ctx.save_for_backward(y, *params)       # the parameters: autograd refuses a backward after an in-place update of one
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        y = ctx.saved_tensors[0]
+        return (None, None, None) + tuple(ctx.gen._backward(ctx.state, y, dy))
+
+
 class HifiganGenerator(nn.Module):
-    """HiFi-GAN generator (reference urhythmic/vocoder.py:23-114), inference only.  x (B, in_channels, N) -> (B, 1, N * prod(factors))."""
+    """HiFi-GAN generator (reference urhythmic/vocoder.py:23-114).  x (B, in_channels, N) -> (B, 1, N * prod(factors)).  Inference
+    only until `trainable()` is called; then forward() under grad mode carries the parameter gradients."""
 
     def __init__(self, in_channels=256, resblock_dilation_sizes=((1, 3, 5), (1, 3, 5), (1, 3, 5)), resblock_kernel_sizes=(3, 7, 11),
                  upsample_kernel_sizes=(20, 16, 4, 4), upsample_channels=512, upsample_factors=(10, 8, 2, 2), sample_rate=16000):
@@ -136,6 +160,17 @@ class HifiganGenerator(nn.Module):
                 self.resblocks.append(ResBlock(ch, k, d))
         self.conv_post = _WNConv((1, ch, 7), 1, ch * 7)
         self._ops = {}            # compute dtype -> {layer name: (operand, bias fp32)}
+        self._trainable = False
+
+    def trainable(self, mode=True):
+        """Switch the backward pass on (or off again; off is the default and changes nothing).  On: forward() under grad mode
+        returns a tensor with a grad_fn whose backward fills the .grad of every parameter, and EVERY call -- under no_grad and
+        the batched ones too -- folds its operands from the live parameters, so an optimiser's in-place update is seen by the
+        next call.  An input that requires grad is refused in either mode.  Under Fn.set_compute_dtype(bfloat16) the backward runs in
+        bf16 (fp32 accumulation, fp32 parameter gradients) while the training forward keeps fp32 activations (_forward_train)."""
+        self._trainable = bool(mode)
+        self._drop_cache()
+        return self
 
     # ---- checkpoint forms -------------------------------------------------------------------------------------------------
     def _leaves(self):
@@ -231,19 +266,138 @@ class HifiganGenerator(nn.Module):
         plan.append(dict(kind="conv_out", layer="conv_post", src=cur, k=7, cin=ch, slope=POST_SLOPE, mul=mul))
         return plan
 
+    def _train_plan(self):
+        """launch_plan() with every convolution's output in a buffer of its own (the backward reads them all): the ping-pong
+        buffers t{i} / a{i} / b{i} become `<layer>.out`."""
+        plan, cur = [], {}
+        for e in self.launch_plan():
+            e = dict(e)
+            for key in ("src", "res"):
+                if key in e:
+                    e[key] = cur.get(e[key], e[key])
+            dst = e.get("dst")
+            if dst is not None and dst[0] in "tab" and dst[1:].isdigit():
+                cur[dst] = e["dst"] = e["layer"] + ".out"
+            plan.append(e)
+        return plan
+
+    def backward_plan(self):
+        """What one backward pass launches, in order: dicts with `kind` in BWD_KINDS.  `d:<buffer>` names the gradient of a forward
+        buffer of _train_plan().  Per convolution: the weight / bias partials ("wgrad"; conv_post's come from "conv_out_bwd"), the
+        "finish" launch that writes the parameters' gradients, and -- except for conv_pre, whose input is data -- the data gradient.
+        Every gradient buffer is written by one launch; d:up{i} is accumulated by the first unit of every ResBlock of the stage.
+        The residual x' = conv2(..) + x is the `res` of conv1's data gradient, and the 1 / num_kernels of the MRF average is the
+        `scale` of the launch that produces d:s{i}.  _backward() executes exactly this list."""
+        nk = self.num_kernels
+        plan, pending, written = [], {}, set()
+        for e in reversed(self._train_plan()):
+            kind, layer = e["kind"], e.get("layer")
+            if kind == "input":
+                continue
+            if kind == "conv_out":
+                plan.append(dict(kind="conv_out_bwd", layer=layer, src=e["src"], dst="d:" + e["src"], k=e["k"], cin=e["cin"], slope=e["slope"],
+                                 scale=1.0 / nk))
+                plan.append(dict(kind="finish", layer=layer, mode=2, u=1))
+                continue
+            dy = "d:" + e["dst"]
+            if kind == "tconv1d":
+                plan.append(dict(kind="wgrad", layer=layer, conv=1, dy=dy, src=e["src"], k=e["k"], step=e["u"], slope=e["slope"]))
+                plan.append(dict(kind="finish", layer=layer, mode=1, u=e["u"]))
+                plan.append(dict(kind="tconv1d_dgrad", layer=layer, dy=dy, mask=e["src"], dst="d:" + e["src"], k=e["k"], u=e["u"], cin=e["cin"],
+                                 slope=e["slope"], scale=1.0 if e["src"] == "pre" else 1.0 / nk))
+                continue
+            plan.append(dict(kind="wgrad", layer=layer, conv=0, dy=dy, src=e["src"], k=e["k"], step=e["dil"], slope=e["slope"]))
+            plan.append(dict(kind="finish", layer=layer, mode=0, u=1))
+            if layer == "conv_pre":
+                continue
+            d = dict(kind="conv1d_dgrad", layer=layer, dy=dy, mask=e["src"], dst="d:" + e["src"], k=e["k"], dil=e["dil"], cin=e["cin"],
+                     slope=e["slope"], scale=1.0, accumulate=False)
+            if "res" in e:                       # convs2: the residual's share of d:x waits for convs1's data gradient
+                pending[e["res"]] = dy
+            else:                                # convs1
+                d.update(res=pending.pop(e["src"]), accumulate=e["src"] in written)
+                written.add(e["src"])
+            plan.append(d)
+        return plan
+
+    # ---- training ---------------------------------------------------------------------------------------------------------
+    def _forward_train(self, x, taps):
+        """The training forward keeps fp32 activations in EITHER compute mode: a leaky-relu mask is the sign of a stored
+        pre-activation, and a bf16 forward's error flips hundreds of them (370 of 170 880 on the tests' tiny model, which alone
+        puts every gradient 5 - 20 % from the exact one).  In bf16 mode the backward's GEMMs run in bf16 over copies of the stored
+        tensors that one cast launch each (the input kernel) rounds to bf16 -- a rounding keeps the sign, so no mask flips."""
+        dtype = Fn.compute_dtype()
+        ops, state = {}, {}
+        for name, m in self._leaves():
+            mode, u = self._layer_mode(name)
+            if m.normed:
+                v, g = m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
+            else:
+                v, g = m.weight.detach().float().contiguous(), None
+            w32, op = KV.hifigan_fold(mode, v, g, torch.float32, u=u)
+            opT = KV.hifigan_fold_bwd(mode, w32, dtype, u=u) if mode != 2 and name != "conv_pre" else None
+            ops[name] = (op, m.bias.detach().float().contiguous())
+            state[name] = (v, g, op, opT)
+        bufs = {}
+        B, _, N = x.shape
+        y = self._run(x.detach(), B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps, plan=self._train_plan(), ops=ops, keep=bufs,
+                      dtype=torch.float32)
+        if dtype != torch.float32:
+            bufs = {k: KV.hifigan_input(v, v.shape[0], v.shape[1], v.shape[2], (v.stride(0), v.stride(1), v.stride(2)), dtype)
+                    for k, v in bufs.items()}
+        state[":bufs"], state[":dtype"] = bufs, dtype
+        return y.view(B, 1, -1), state
+
+    def _backward(self, state, y, dy):
+        """Gradients of every parameter, in named_parameters() order, from dy (B, 1, L): executes backward_plan()."""
+        bufs, dtype = state[":bufs"], state[":dtype"]
+        B, L = y.shape[0], y.shape[-1]
+        y2, dy2 = y.detach().reshape(B, L).contiguous(), dy.detach().float().reshape(B, L).contiguous()
+        grads, parts, out = {}, None, {}
+        with torch.no_grad():
+            for e in self.backward_plan():
+                kind, layer = e["kind"], e["layer"]
+                v, g, op, opT = state[layer]
+                if kind == "conv_out_bwd":
+                    grads[e["dst"]], wp, bp = KV.hifigan_conv_out_bwd(bufs[e["src"]], op, y2, dy2, e["k"], slope=e["slope"], scale=e["scale"])
+                    parts = (wp, bp)
+                elif kind == "wgrad":
+                    parts = KV.hifigan_wgrad(e["conv"], grads[e["dy"]], bufs[e["src"]], e["k"], e["step"], slope=e["slope"])
+                elif kind == "finish":
+                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], v, g, u=e["u"])
+                    parts = None
+                elif kind == "tconv1d_dgrad":
+                    grads[e["dst"]] = KV.hifigan_tconv1d_dgrad(grads[e["dy"]], opT, e["k"], e["u"], e["cin"], mask_src=bufs[e["mask"]],
+                                                               slope=e["slope"], scale=e["scale"])
+                else:
+                    res = grads[e["res"]] if e.get("res") else None
+                    grads[e["dst"]] = KV.hifigan_conv1d_dgrad(grads[e["dy"]], opT, e["k"], e["dil"], e["cin"], mask_src=bufs[e["mask"]],
+                                                              slope=e["slope"], res=res, accumulate=e["accumulate"], scale=e["scale"],
+                                                              out=grads.get(e["dst"]))
+        result = []
+        for name, p in self.named_parameters():
+            layer, leaf = name.rsplit(".", 1)
+            gw, gg, gb = out[layer]
+            t = gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)
+            result.append(t.view_as(p).to(p.dtype))
+        return result
+
     # ---- execution --------------------------------------------------------------------------------------------------------
-    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None):
+    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None, plan=None, ops=None, keep=None, dtype=None):
         if not x.is_cuda:
             raise RuntimeError("HifiganGenerator needs GPU tensors (there is no CPU path)")
         if torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError("HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("HifiganGenerator input: float32 or bfloat16")
-        dtype = Fn.compute_dtype()
-        ops = self._operands(dtype)
-        bufs, y = {}, None
+        dtype = Fn.compute_dtype() if dtype is None else dtype
+        if ops is None:
+            if self._trainable:                  # an optimiser updates the parameters in place: fold from the live values
+                self._drop_cache()
+            ops = self._operands(dtype)
+        bufs, y = ({} if keep is None else keep), None
         with torch.no_grad():
-            for e in self.launch_plan():
+            for e in (self.launch_plan() if plan is None else plan):
                 kind = e["kind"]
                 if kind == "input":
                     bufs[e["dst"]] = KV.hifigan_input(x.detach(), B, N, e["cout"], strides, dtype, a=a, b=b, vlens=vlens)
@@ -273,6 +427,14 @@ class HifiganGenerator(nn.Module):
         if x.dim() != 3 or x.shape[1] != self.in_channels:
             raise ValueError(f"HifiganGenerator: x (B, {self.in_channels}, N) expected, got {tuple(x.shape)}")
         B, _, N = x.shape
+        if self._trainable and torch.is_grad_enabled():
+            if x.requires_grad:
+                raise NotImplementedError("HifiganGenerator computes no input gradient: the units / mel are data (detach the input)")
+            if not x.is_cuda:
+                raise RuntimeError("HifiganGenerator needs GPU tensors (there is no CPU path)")
+            if x.dtype not in (torch.float32, torch.bfloat16):
+                raise TypeError("HifiganGenerator input: float32 or bfloat16")
+            return _GeneratorFunction.apply(self, x, taps, *[p for _, p in self.named_parameters()])
         y = self._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps)
         return y.view(B, 1, -1)
 
@@ -281,7 +443,8 @@ class HifiganGenerator(nn.Module):
         list of B waveforms of lens[b] * prod(upsample_factors) samples, each what the utterance gets alone.
         lens: a list / CPU tensor, or an int32 device tensor (what the kernels read).  Only the slicing of the result needs the
         lengths on the host: pass them as host_lens beside a device tensor and the call never waits for the device; without
-        host_lens a device tensor is read back AFTER every launch has been queued."""
+        host_lens a device tensor is read back AFTER every launch has been queued.
+        Inference only, also after trainable(): the result has no grad_fn (ragged batches are not trained on)."""
         if xs.dim() != 3 or xs.shape[2] != self.in_channels:
             raise ValueError(f"HifiganGenerator: xs (B, Nmax, {self.in_channels}) expected, got {tuple(xs.shape)}")
         B, N, _ = xs.shape
@@ -330,5 +493,6 @@ class HifiganVocoder:
         return y[0], sr
 
     def decode_batch(self, cs, lens, host_lens=None):
+        """Inference only, also over a generator that is trainable(): the waveforms have no grad_fn."""
         a, b = self._affine(cs.device)
         return self.generator.forward_batch(cs, lens, a=a, b=b, host_lens=host_lens), self.generator.sample_rate
