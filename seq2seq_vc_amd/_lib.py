@@ -33,8 +33,8 @@ def build_library(force=False, verbose=True, debug_exec=False):
     if not debug_exec and os.environ.get("S2SVC_LIB"):
         lib_path = os.path.join(CSRC, "libs2svc_hip.so")        # never build over an alternative library named by S2SVC_LIB
     srcs = [os.path.join(CSRC, f) for f in sources()]
-    deps = srcs + [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_common.h"),
-                   os.path.join(_HERE, "..", "include", "s2svc_hip.h")]
+    deps = srcs + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [
+        os.path.join(_HERE, "..", "include", "s2svc_hip.h")]
     if not force and os.path.exists(lib_path):
         newest = max(os.path.getmtime(p) for p in deps)
         if os.path.getmtime(lib_path) >= newest:

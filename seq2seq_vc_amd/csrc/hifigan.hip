@@ -10,33 +10,11 @@
 // the zero padding the reference applies at the utterance's own end, written as zero.  The reduction of one output element runs in
 // one fixed order that does not depend on the batch, so a row of a batch gets the bits it gets alone.
 //
-// Tile: 128 frames x BN columns per workgroup of 4 wavefronts (32 frames x BN columns each), 32 input channels per step.  The A
-// tile is staged once per channel step WITH its halo (<= 50 frames: k = 11, dil = 5) and every tap reads it from LDS at a row
-// offset, so an activation is fetched (and passed through leaky_relu) once for all k taps; the weight operand of up to 4 taps is
-// staged beside it.  LDS rows are padded by 16 bytes.
-#include "gemm_common.h"
+// The tile (128 frames x BN columns per workgroup, the A tile staged once per channel step with its halo) is csrc/hifigan_tile.h,
+// shared with the data gradient; this file supplies its A loader (frames with vlens, leaky_relu) and its epilogue.
+#include "hifigan_tile.h"
 
 namespace {
-
-constexpr int HG_BM = 128, HG_KC = 32, HG_TG = 4, HG_MAXSPAN = 50;
-
-template <typename T> struct HgFrag;
-template <> struct HgFrag<bf16_t> {
-  static constexpr int VEC = 8, KSTEP = 32;      // one v_mfma_f32_16x16x32_bf16 per step
-  typedef bf16x8_t type;
-  static __device__ __forceinline__ f32x4_t mma(type a, type b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct HgFrag<float> {
-  static constexpr int VEC = 4, KSTEP = 16;      // four v_mfma_f32_16x16x4_f32 per step (lane element e <-> k = 4 * (lane >> 4) + e)
-  typedef f32x4_t type;
-  static __device__ __forceinline__ f32x4_t mma(type a, type b, f32x4_t c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], c, 0, 0, 0);
-    return c;
-  }
-};
-
-__device__ __forceinline__ float hg_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // one 16-byte vector of the A operand: load (vector or element-wise with a channel bound), leaky_relu, back to 16 bytes
 __device__ __forceinline__ uint4 hg_load_act(const float* p, int nvalid, bool vec, float slope) {
@@ -78,9 +56,8 @@ struct HgArgs {
   const void* res;       // (B, Tout, Cout) or NULL
   void* out;             // (B, Tout, Cout)
   const int32_t* vlens;  // (B) or NULL
-  int B, Tin, Cin, Cinp, Cout, N, ntaps;
-  int tstep, toff0, offmin, span;   // tap j reads frame i + j * tstep + toff0; offmin = the smallest offset, span = largest - smallest
-  int Trows, tiles_per_b, Tout, u, pad;
+  HgGeom g;              // tap j reads frame i + j * tstep + toff0
+  int B, Tin, Cin, Cinp, Cout, N, Tout, u;
   int vmul_in, vmul_out;
   float slope, scale;
   int accumulate, act_tanh;
@@ -88,21 +65,8 @@ struct HgArgs {
 
 template <typename T, int BN>
 __global__ __launch_bounds__(256) void hifigan_gemm_kernel(const HgArgs a) {
-  typedef HgFrag<T> F;
-  typedef typename F::type frag_t;
-  constexpr int VEC = F::VEC;
-  constexpr int VPR = HG_KC / VEC;                       // 16-byte vectors per LDS row
-  constexpr int ROWB = HG_KC * (int)sizeof(T) + 16;      // LDS row in bytes, padded
-  constexpr int NT = BN / 16;
-  constexpr int KS = HG_KC / F::KSTEP;
-  __shared__ __attribute__((aligned(16))) unsigned char sA[(HG_BM + HG_MAXSPAN) * ROWB];
-  __shared__ __attribute__((aligned(16))) unsigned char sB[HG_TG * BN * ROWB];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int b = blockIdx.x / a.tiles_per_b;
-  const int i0 = (blockIdx.x - b * a.tiles_per_b) * HG_BM;
-  const int n0 = blockIdx.y * BN;
+  const int b = blockIdx.x / a.g.tiles;
+  const int i0 = (blockIdx.x - b * a.g.tiles) * HG_BM;
   int vlen_in = a.Tin, vlen_out = a.Tout;
   if (a.vlens) {
     const int l = a.vlens[b] > 0 ? a.vlens[b] : 0;
@@ -110,87 +74,42 @@ __global__ __launch_bounds__(256) void hifigan_gemm_kernel(const HgArgs a) {
     vlen_out = min(l * a.vmul_out, a.Tout);
   }
   const T* xb = (const T*)a.x + (int64_t)b * a.Tin * a.Cin;
-  const T* W = (const T*)a.w;
-  const int Kp = a.ntaps * a.Cinp;
-  const bool vec_ok = (a.Cin % VEC) == 0;
-  const int R = HG_BM + a.span;
-
-  f32x4_t acc[2][NT];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  for (int c0 = 0; c0 < a.Cinp; c0 += HG_KC) {
-    __syncthreads();                                     // the previous step's fragments have been read
-    for (int idx = tid; idx < R * VPR; idx += 256) {
-      const int r = idx / VPR, v = idx - r * VPR;
-      const int t = i0 + r + a.offmin, c = c0 + v * VEC;
-      uint4 val = make_uint4(0u, 0u, 0u, 0u);
-      if (t >= 0 && t < vlen_in && c < a.Cin) val = hg_load_act(xb + (int64_t)t * a.Cin + c, a.Cin - c, vec_ok, a.slope);
-      *reinterpret_cast<uint4*>(sA + r * ROWB + v * 16) = val;
-    }
-    for (int tg = 0; tg < a.ntaps; tg += HG_TG) {
-      const int gn = min(HG_TG, a.ntaps - tg);
-      if (tg > 0) __syncthreads();
-      for (int idx = tid; idx < gn * BN * VPR; idx += 256) {
-        const int tapi = idx / (BN * VPR), rem = idx - tapi * (BN * VPR);
-        const int nn = rem / VPR, v = rem - nn * VPR;
-        uint4 val = make_uint4(0u, 0u, 0u, 0u);
-        if (n0 + nn < a.N) val = *reinterpret_cast<const uint4*>(W + (int64_t)(n0 + nn) * Kp + (tg + tapi) * a.Cinp + c0 + v * VEC);
-        *reinterpret_cast<uint4*>(sB + (tapi * BN + nn) * ROWB + v * 16) = val;
-      }
-      __syncthreads();
-      for (int tapi = 0; tapi < gn; ++tapi) {
-        const int arow = wave * 32 + lr + (tg + tapi) * a.tstep + a.toff0 - a.offmin;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const int koff = ks * 64 + lg * 16;
-          frag_t fa[2], fb[NT];
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) fa[mt] = *reinterpret_cast<const frag_t*>(sA + (arow + mt * 16) * ROWB + koff);
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) fb[nt] = *reinterpret_cast<const frag_t*>(sB + (tapi * BN + nt * 16 + lr) * ROWB + koff);
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = F::mma(fa[mt], fb[nt], acc[mt][nt]);
-        }
-      }
-    }
-  }
-
-  // epilogue: bias, residual, scale / accumulate, tanh in fp32; one rounding at the store; absent frames are written as zero
+  const bool vec_ok = (a.Cin % HgFrag<T>::VEC) == 0;
   T* outb = (T*)a.out + (int64_t)b * a.Tout * a.Cout;
   const T* resb = a.res ? (const T*)a.res + (int64_t)b * a.Tout * a.Cout : nullptr;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int n = n0 + nt * 16 + lr;
-    if (n >= a.N) continue;
-    int p = 0, o = n;
-    if (a.u > 1) { p = n / a.Cout; o = n - p * a.Cout; }
-    const float bv = a.bias ? a.bias[o] : 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + wave * 32 + mt * 16 + lg * 4 + r;
-        if (i >= a.Trows) continue;
-        const int t = a.u * i + p - a.pad;
-        if (t < 0 || t >= a.Tout) continue;
-        const int64_t at = (int64_t)t * a.Cout + o;
-        float v = 0.f;
-        if (t < vlen_out) {
-          v = acc[mt][nt][r] + bv;
-          if (resb) v += ldf(resb + at);
-          v *= a.scale;
-          if (a.accumulate) v += ldf(outb + at);
-          if (a.act_tanh) v = tanhf(v);
-        }
-        stf(outb + at, v);
-      }
-  }
+  hg_tile<T, BN>(
+      a.g, (const T*)a.w, a.Cinp, a.N, i0, blockIdx.y * BN,
+      [&](int r, int c) {
+        const int t = i0 + r + a.g.offmin;
+        if (t < 0 || t >= vlen_in || c >= a.Cin) return make_uint4(0u, 0u, 0u, 0u);
+        return hg_load_act(xb + (int64_t)t * a.Cin + c, a.Cin - c, vec_ok, a.slope);
+      },
+      // epilogue: bias, residual, scale / accumulate, tanh in fp32; one rounding at the store; absent frames are written as zero
+      [&](int n) {
+        int p = 0, o = n;
+        if (a.u > 1) { p = n / a.Cout; o = n - p * a.Cout; }
+        const float bv = a.bias ? a.bias[o] : 0.f;
+        return [&, p, o, bv](int i, float acc) {
+          const int t = a.u * i + p - a.g.pad;
+          if (t < 0 || t >= a.Tout) return;
+          const int64_t at = (int64_t)t * a.Cout + o;
+          float v = 0.f;
+          if (t < vlen_out) {
+            v = acc + bv;
+            if (resb) v += ldf(resb + at);
+            v *= a.scale;
+            if (a.accumulate) v += ldf(outb + at);
+            if (a.act_tanh) v = tanhf(v);
+          }
+          stf(outb + at, v);
+        };
+      });
 }
+
+struct HgGemm {
+  static constexpr const char* name = "hifigan_gemm_kernel";
+  template <typename T, int BN> static constexpr auto fn = hifigan_gemm_kernel<T, BN>;
+};
 
 // The output convolution C -> 1 (vocoder.py:85, 103-105: leaky_relu, conv_post, tanh): a dot product of k * C values per sample,
 // bandwidth bound -- one lane per output sample, a wavefront per 64 consecutive samples, no MFMA tile with 15 dead columns.
@@ -304,63 +223,37 @@ __global__ __launch_bounds__(256) void hifigan_fold_kernel(int mode, int D0, int
   }
 }
 
-int hg_launch(int dtype, const HgArgs& a, hipStream_t st) {
-  dim3 grid(a.B * a.tiles_per_b, 1), block(256);
-  const int bn = a.N > 32 ? 64 : (a.N > 16 ? 32 : 16);
-  grid.y = (a.N + bn - 1) / bn;
-  if (dtype == S2S_F32) {
-    if (bn == 64) hipLaunchKernelGGL((hifigan_gemm_kernel<float, 64>), grid, block, 0, st, a);
-    else if (bn == 32) hipLaunchKernelGGL((hifigan_gemm_kernel<float, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hifigan_gemm_kernel<float, 16>), grid, block, 0, st, a);
-  } else {
-    if (bn == 64) hipLaunchKernelGGL((hifigan_gemm_kernel<bf16_t, 64>), grid, block, 0, st, a);
-    else if (bn == 32) hipLaunchKernelGGL((hifigan_gemm_kernel<bf16_t, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hifigan_gemm_kernel<bf16_t, 16>), grid, block, 0, st, a);
-  }
-  S2S_CHECK_LAUNCH("hifigan_gemm_kernel");
-  return 0;
-}
-
 }  // namespace
 
-extern "C" int s2svc_hifigan_cin_padded(int C) { return (C + HG_KC - 1) / HG_KC * HG_KC; }
+extern "C" int s2svc_hifigan_cin_padded(int C) { return hg_pad32(C); }
 
 extern "C" int s2svc_hifigan_conv1d(int dtype, int B, int T, int Cin, int Cout, int k, int dil, const void* x, const void* w_op,
                                     const float* bias, float slope, const void* res, int accumulate, float scale, int act_tanh,
                                     void* out, const int32_t* vlens, int vmul, void* stream) {
   S2S_REQUIRE(dtype == S2S_F32 || dtype == S2S_BF16, "hifigan_conv1d: dtype 0 (float32) or 1 (bfloat16)");
   S2S_REQUIRE(B >= 1 && T >= 1 && Cin >= 1 && Cin <= 512 && Cout >= 1 && Cout <= 512, "hifigan_conv1d: 1 <= C_in, C_out <= 512");
-  S2S_REQUIRE(k >= 1 && k <= 11 && (k & 1) && dil >= 1 && dil <= 5, "hifigan_conv1d: k odd <= 11, dil 1..5");
   S2S_REQUIRE(x && w_op && out && vmul >= 1, "hifigan_conv1d: null pointer or vmul < 1");
-  S2S_REQUIRE((int64_t)B * ((T + HG_BM - 1) / HG_BM) < (1ll << 31), "hifigan_conv1d: too many row tiles");
   HgArgs a = {};
+  if (const int rc = hg_conv1d_geom("hifigan_conv1d", B, T, k, dil, a.g)) return rc;
   a.x = x; a.w = w_op; a.bias = bias; a.res = res; a.out = out; a.vlens = vlens;
-  a.B = B; a.Tin = T; a.Cin = Cin; a.Cinp = s2svc_hifigan_cin_padded(Cin); a.Cout = Cout; a.N = Cout; a.ntaps = k;
-  a.tstep = dil; a.toff0 = -((k - 1) / 2) * dil; a.offmin = a.toff0; a.span = (k - 1) * dil;
-  a.Trows = T; a.tiles_per_b = (T + HG_BM - 1) / HG_BM; a.Tout = T; a.u = 1; a.pad = 0;
+  a.B = B; a.Tin = T; a.Cin = Cin; a.Cinp = hg_pad32(Cin); a.Cout = Cout; a.N = Cout; a.Tout = T; a.u = 1;
   a.vmul_in = vmul; a.vmul_out = vmul;
   a.slope = slope; a.scale = scale; a.accumulate = accumulate; a.act_tanh = act_tanh;
-  return hg_launch(dtype, a, (hipStream_t)stream);
+  return hg_launch<HgGemm>(dtype, a, (hipStream_t)stream);
 }
 
 extern "C" int s2svc_hifigan_tconv1d(int dtype, int B, int Tin, int Cin, int Cout, int k, int u, const void* x, const void* w_op,
                                      const float* bias, float slope, void* out, const int32_t* vlens, int vmul, void* stream) {
   S2S_REQUIRE(dtype == S2S_F32 || dtype == S2S_BF16, "hifigan_tconv1d: dtype 0 (float32) or 1 (bfloat16)");
   S2S_REQUIRE(B >= 1 && Tin >= 1 && Cin >= 1 && Cin <= 512 && Cout >= 1 && Cout <= 512, "hifigan_tconv1d: 1 <= C_in, C_out <= 512");
-  S2S_REQUIRE(u >= 1 && k >= u && ((k - u) & 1) == 0, "hifigan_tconv1d: k >= u and (k - u) even (padding (k - u) / 2 gives T_out = u T_in)");
-  const int ntaps = (k + u - 1) / u, pad = (k - u) / 2;
-  S2S_REQUIRE(ntaps - 1 <= HG_MAXSPAN, "hifigan_tconv1d: more than 51 taps per phase");
   S2S_REQUIRE(x && w_op && out && vmul >= 1, "hifigan_tconv1d: null pointer or vmul < 1");
-  S2S_REQUIRE((int64_t)Tin * u < (1ll << 31) / 512, "hifigan_tconv1d: output too long");
-  S2S_REQUIRE((int64_t)B * ((Tin + (pad + u - 1) / u + HG_BM - 1) / HG_BM) < (1ll << 31), "hifigan_tconv1d: too many row tiles");
   HgArgs a = {};
+  if (const int rc = hg_tconv1d_geom("hifigan_tconv1d", B, Tin, k, u, false, a.g)) return rc;
   a.x = x; a.w = w_op; a.bias = bias; a.res = nullptr; a.out = out; a.vlens = vlens;
-  a.B = B; a.Tin = Tin; a.Cin = Cin; a.Cinp = s2svc_hifigan_cin_padded(Cin); a.Cout = Cout; a.N = u * Cout; a.ntaps = ntaps;
-  a.tstep = -1; a.toff0 = 0; a.offmin = -(ntaps - 1); a.span = ntaps - 1;
-  a.Trows = Tin + (pad + u - 1) / u; a.tiles_per_b = (a.Trows + HG_BM - 1) / HG_BM; a.Tout = u * Tin; a.u = u; a.pad = pad;
+  a.B = B; a.Tin = Tin; a.Cin = Cin; a.Cinp = hg_pad32(Cin); a.Cout = Cout; a.N = u * Cout; a.Tout = u * Tin; a.u = u;
   a.vmul_in = vmul; a.vmul_out = vmul * u;
   a.slope = slope; a.scale = 1.f; a.accumulate = 0; a.act_tanh = 0;
-  return hg_launch(dtype, a, (hipStream_t)stream);
+  return hg_launch<HgGemm>(dtype, a, (hipStream_t)stream);
 }
 
 extern "C" int s2svc_hifigan_conv_out(int dtype, int B, int T, int C, int k, const void* x, const float* w, const float* bias,
@@ -403,7 +296,7 @@ extern "C" int s2svc_hifigan_fold(int mode, int D0, int D1, int k, int u, const 
   S2S_REQUIRE(mode >= 0 && mode <= 2 && D0 >= 1 && D1 >= 1 && k >= 1 && u >= 1 && v, "hifigan_fold: bad mode / shape or null pointer");
   S2S_REQUIRE(op_dtype == S2S_F32 || op_dtype == S2S_BF16, "hifigan_fold: operand dtype 0 / 1");
   S2S_REQUIRE(mode != 2 || (D0 == 1 && op_dtype == S2S_F32), "hifigan_fold: the output convolution's operand is fp32, one output channel");
-  const int Cinp = s2svc_hifigan_cin_padded(mode == 1 ? D0 : D1);
+  const int Cinp = hg_pad32(mode == 1 ? D0 : D1);
   hipStream_t st = (hipStream_t)stream;
   if (op_dtype == S2S_F32)
     hipLaunchKernelGGL(hifigan_fold_kernel<float>, dim3(D0), dim3(256), 0, st, mode, D0, D1, k, mode == 1 ? u : 1, Cinp, g, v, w32, (float*)w_op);

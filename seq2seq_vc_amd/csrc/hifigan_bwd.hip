@@ -2,10 +2,10 @@
 // loss_generator.backward() through seq2seq_vc/urhythmic/vocoder.py:23-202).  The forward is csrc/hifigan.hip, unchanged; the stored
 // activations are the raw pre-activations (channel-last), leaky_relu is applied as they are staged.
 //
-//   data gradient     hifigan_dgrad_kernel: the forward's implicit-GEMM tile (128 frames x BN columns, 32-channel steps, the halo
-//                     staged once for all taps) over a flipped / transposed operand (hifigan_fold_bwd_kernel), with the epilogue
-//                     out = [out +] scale * (lrelu'(mask_src) * acc [+ res]).  The transposed convolution's data gradient is the same
-//                     kernel on the forward's own GEMM view of dy: (rows, u * C_out) at a flat offset of -pad * C_out elements.
+//   data gradient     hifigan_dgrad_kernel: the forward's implicit-GEMM tile (csrc/hifigan_tile.h, the same body) over a flipped /
+//                     transposed operand (hifigan_fold_bwd_kernel); this file supplies the A loader (a flat view with bounds) and
+//                     the epilogue out = [out +] scale * (lrelu'(mask_src) * acc [+ res]).  The transposed convolution's data gradient
+//                     is the same kernel on the forward's own GEMM view of dy: (rows, u * C_out) at a flat offset of -pad * C_out.
 //   weight gradient   hifigan_wgrad_kernel: dw[m][tap][c] = sum over frames of dy[i][m] * lrelu(x)[i + off(tap)][c], both operands
 //                     reduced over their slow axis.  A workgroup owns a 32 x 32 x taps block of the result and ONE chunk of frames
 //                     (chunk edges depend on the shapes only); it writes an fp32 partial, and the column sums of dy (the bias
@@ -15,31 +15,12 @@
 //   conv_post         hifigan_conv_out_bwd_kernel: tanh derivative, the C -> 1 data gradient with its mask, weight / bias partials.
 //
 // Every sum runs in one order that depends on the shapes only: two passes over the same inputs give the same bits.
-#include "gemm_common.h"
+#include "hifigan_tile.h"
 
 namespace {
 
-constexpr int HB_BM = 128, HB_KC = 32, HB_TG = 4, HB_MAXSPAN = 50;
 constexpr int HW_TS = 32, HW_MAXTAPS = 12, HW_ITEMS = 6;      // wgrad: frames per step; (tap, 16-row half) items per wavefront
 constexpr int HO_CHUNK = 256, HO_MAXK = 11;                   // conv_post backward: frames per workgroup
-
-template <typename T> struct HbFrag;
-template <> struct HbFrag<bf16_t> {
-  static constexpr int VEC = 8, KSTEP = 32;
-  typedef bf16x8_t type;
-  static __device__ __forceinline__ f32x4_t mma(type a, type b, f32x4_t c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct HbFrag<float> {
-  static constexpr int VEC = 4, KSTEP = 16;
-  typedef f32x4_t type;
-  static __device__ __forceinline__ f32x4_t mma(type a, type b, f32x4_t c) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], c, 0, 0, 0);
-    return c;
-  }
-};
-
-__device__ __forceinline__ float hb_lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 template <typename T> __device__ __forceinline__ uint4 hb_pack(const float (&f)[8]);
 template <> __device__ __forceinline__ uint4 hb_pack<float>(const float (&f)[8]) {
@@ -65,7 +46,7 @@ __device__ __forceinline__ uint4 hb_load_view(const T* base, int64_t flat, int64
   }
   if (slope != 0.f) {
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) f[e] = hb_lrelu(f[e], slope);
+    for (int e = 0; e < VEC; ++e) f[e] = hg_lrelu(f[e], slope);
   }
   return hb_pack<T>(f);
 }
@@ -76,127 +57,48 @@ __device__ __forceinline__ uint4 hb_load_view(const T* base, int64_t flat, int64
 struct HbArgs {
   const void* a;         // the gradient: per utterance a flat tensor of La elements, viewed as rows of Ka columns at offset -aoff
   const void* w;         // [N][ntaps * Kap], reduction index tap * Kap + column (hifigan_fold_bwd)
-  const void* mask;      // (B, Trows, N) or NULL: the forward's raw input of the layer
-  const void* res;       // (B, Trows, N) or NULL
-  void* out;             // (B, Trows, N)
+  const void* mask;      // (B, rows, N) or NULL: the forward's raw input of the layer
+  const void* res;       // (B, rows, N) or NULL
+  void* out;             // (B, rows, N)
   int64_t La;
-  int B, Ka, Kap, aoff, N, ntaps;
-  int tstep, toff0, offmin, span;    // tap j reads view row i + j * tstep + toff0
-  int Trows, tiles_per_b;
+  HgGeom g;              // tap j reads view row i + j * tstep + toff0
+  int B, Ka, Kap, aoff, N;
   float slope, scale;
   int accumulate, vec_ok;
 };
 
 template <typename T, int BN>
 __global__ __launch_bounds__(256) void hifigan_dgrad_kernel(const HbArgs a) {
-  typedef HbFrag<T> F;
-  typedef typename F::type frag_t;
-  constexpr int VEC = F::VEC;
-  constexpr int VPR = HB_KC / VEC;
-  constexpr int ROWB = HB_KC * (int)sizeof(T) + 16;
-  constexpr int NT = BN / 16;
-  constexpr int KS = HB_KC / F::KSTEP;
-  __shared__ __attribute__((aligned(16))) unsigned char sA[(HB_BM + HB_MAXSPAN) * ROWB];
-  __shared__ __attribute__((aligned(16))) unsigned char sB[HB_TG * BN * ROWB];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, lg = lane >> 4;
-  const int b = blockIdx.x / a.tiles_per_b;
-  const int i0 = (blockIdx.x - b * a.tiles_per_b) * HB_BM;
-  const int n0 = blockIdx.y * BN;
+  const int b = blockIdx.x / a.g.tiles;
+  const int i0 = (blockIdx.x - b * a.g.tiles) * HG_BM;
   const T* ab = (const T*)a.a + (int64_t)b * a.La;
-  const T* W = (const T*)a.w;
-  const int Kp = a.ntaps * a.Kap;
-  const int R = HB_BM + a.span;
-
-  f32x4_t acc[2][NT];
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  for (int c0 = 0; c0 < a.Kap; c0 += HB_KC) {
-    __syncthreads();
-    for (int idx = tid; idx < R * VPR; idx += 256) {
-      const int r = idx / VPR, v = idx - r * VPR;
-      const int c = c0 + v * VEC;
-      const int64_t flat = (int64_t)(i0 + r + a.offmin) * a.Ka + c - a.aoff;
-      uint4 val = make_uint4(0u, 0u, 0u, 0u);
-      if (c < a.Ka) val = hb_load_view<T>(ab, flat, a.La, c, a.Ka, a.vec_ok != 0, 0.f);
-      *reinterpret_cast<uint4*>(sA + r * ROWB + v * 16) = val;
-    }
-    for (int tg = 0; tg < a.ntaps; tg += HB_TG) {
-      const int gn = min(HB_TG, a.ntaps - tg);
-      if (tg > 0) __syncthreads();
-      for (int idx = tid; idx < gn * BN * VPR; idx += 256) {
-        const int tapi = idx / (BN * VPR), rem = idx - tapi * (BN * VPR);
-        const int nn = rem / VPR, v = rem - nn * VPR;
-        uint4 val = make_uint4(0u, 0u, 0u, 0u);
-        if (n0 + nn < a.N) val = *reinterpret_cast<const uint4*>(W + (int64_t)(n0 + nn) * Kp + (tg + tapi) * a.Kap + c0 + v * VEC);
-        *reinterpret_cast<uint4*>(sB + (tapi * BN + nn) * ROWB + v * 16) = val;
-      }
-      __syncthreads();
-      for (int tapi = 0; tapi < gn; ++tapi) {
-        const int arow = wave * 32 + lr + (tg + tapi) * a.tstep + a.toff0 - a.offmin;
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-          const int koff = ks * 64 + lg * 16;
-          frag_t fa[2], fb[NT];
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt) fa[mt] = *reinterpret_cast<const frag_t*>(sA + (arow + mt * 16) * ROWB + koff);
-#pragma unroll
-          for (int nt = 0; nt < NT; ++nt) fb[nt] = *reinterpret_cast<const frag_t*>(sB + (tapi * BN + nt * 16 + lr) * ROWB + koff);
-#pragma unroll
-          for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = F::mma(fa[mt], fb[nt], acc[mt][nt]);
-        }
-      }
-    }
-  }
-
-  // epilogue: out = [out +] scale * (lrelu'(mask) * acc [+ res]) in fp32, one rounding at the store
-  const int64_t ob = (int64_t)b * a.Trows * a.N;
+  const int64_t ob = (int64_t)b * a.g.rows * a.N;
   T* outb = (T*)a.out + ob;
   const T* maskb = a.mask ? (const T*)a.mask + ob : nullptr;
   const T* resb = a.res ? (const T*)a.res + ob : nullptr;
-#pragma unroll
-  for (int nt = 0; nt < NT; ++nt) {
-    const int n = n0 + nt * 16 + lr;
-    if (n >= a.N) continue;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + wave * 32 + mt * 16 + lg * 4 + r;
-        if (i >= a.Trows) continue;
-        const int64_t at = (int64_t)i * a.N + n;
-        float v = acc[mt][nt][r];
-        if (maskb) v = ldf(maskb + at) > 0.f ? v : v * a.slope;
-        if (resb) v += ldf(resb + at);
-        v *= a.scale;
-        if (a.accumulate) v += ldf(outb + at);
-        stf(outb + at, v);
-      }
-  }
+  hg_tile<T, BN>(
+      a.g, (const T*)a.w, a.Kap, a.N, i0, blockIdx.y * BN,
+      [&](int r, int c) {
+        if (c >= a.Ka) return make_uint4(0u, 0u, 0u, 0u);
+        return hb_load_view<T>(ab, (int64_t)(i0 + r + a.g.offmin) * a.Ka + c - a.aoff, a.La, c, a.Ka, a.vec_ok != 0, 0.f);
+      },
+      // epilogue: out = [out +] scale * (lrelu'(mask) * acc [+ res]) in fp32, one rounding at the store
+      [&](int n) {
+        return [&, n](int i, float v) {
+          const int64_t at = (int64_t)i * a.N + n;
+          if (maskb) v = ldf(maskb + at) > 0.f ? v : v * a.slope;
+          if (resb) v += ldf(resb + at);
+          v *= a.scale;
+          if (a.accumulate) v += ldf(outb + at);
+          stf(outb + at, v);
+        };
+      });
 }
 
-int hb_launch(int dtype, const HbArgs& a, hipStream_t st) {
-  dim3 grid(a.B * a.tiles_per_b, 1), block(256);
-  const int bn = a.N > 32 ? 64 : (a.N > 16 ? 32 : 16);
-  grid.y = (a.N + bn - 1) / bn;
-  if (dtype == S2S_F32) {
-    if (bn == 64) hipLaunchKernelGGL((hifigan_dgrad_kernel<float, 64>), grid, block, 0, st, a);
-    else if (bn == 32) hipLaunchKernelGGL((hifigan_dgrad_kernel<float, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hifigan_dgrad_kernel<float, 16>), grid, block, 0, st, a);
-  } else {
-    if (bn == 64) hipLaunchKernelGGL((hifigan_dgrad_kernel<bf16_t, 64>), grid, block, 0, st, a);
-    else if (bn == 32) hipLaunchKernelGGL((hifigan_dgrad_kernel<bf16_t, 32>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((hifigan_dgrad_kernel<bf16_t, 16>), grid, block, 0, st, a);
-  }
-  S2S_CHECK_LAUNCH("hifigan_dgrad_kernel");
-  return 0;
-}
+struct HbDgrad {
+  static constexpr const char* name = "hifigan_dgrad_kernel";
+  template <typename T, int BN> static constexpr auto fn = hifigan_dgrad_kernel<T, BN>;
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // weight and bias gradients: partials per chunk of frames
@@ -208,7 +110,7 @@ struct HwArgs {
   float* bpart;          // [B * ncpu][Na]
   int64_t Ldy;
   int B, Na, aoff, Tin, Cin, ntaps;
-  int tstep, toff0, offmin, span;    // tap j pairs view row i with input frame i + j * tstep + toff0
+  int tstep, toff0, offmin, span;    // tap j pairs view row i with input frame i + j * tstep + toff0 (HgGeom's fields)
   int rows, chunk, ncpu, ctiles;
   float slope;
   int vec_dy, vec_x;
@@ -237,14 +139,14 @@ template <> struct HwLds<bf16_t> {
 
 template <typename T>
 __global__ __launch_bounds__(256) void hifigan_wgrad_kernel(const HwArgs a) {
-  typedef HbFrag<T> F;
+  typedef HgFrag<T> F;
   typedef typename F::type frag_t;
   typedef HwLds<T> L;
   constexpr int VEC = F::VEC;
-  constexpr int VPR = HB_KC / VEC;
+  constexpr int VPR = HG_KC / VEC;
   constexpr int KS = HW_TS / F::KSTEP;
   __shared__ __attribute__((aligned(16))) T sD[HW_TS * L::ROW];
-  __shared__ __attribute__((aligned(16))) T sX[(HW_TS + HB_MAXSPAN) * L::ROW];
+  __shared__ __attribute__((aligned(16))) T sX[(HW_TS + HG_MAXSPAN) * L::ROW];
   __shared__ float sBias[8][32];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -452,7 +354,7 @@ __global__ __launch_bounds__(256) void hifigan_conv_out_bwd_kernel(int B, int Tn
     for (int r = 0; r < nrows; ++r) {
       const int t = r0 + r + j - half;
       if (t < 0 || t >= Tn) continue;
-      float xv = hb_lrelu(ldf(xb + (int64_t)t * C + c), slope);
+      float xv = hg_lrelu(ldf(xb + (int64_t)t * C + c), slope);
       if (sizeof(T) == 2) xv = bf2f(f2bf(xv));               // the rounding the forward's staging applies
       s += sD[r + half] * xv;
     }
@@ -483,9 +385,6 @@ __global__ __launch_bounds__(256) void hifigan_fold_bwd_kernel(int mode, int D0,
   }
 }
 
-inline int hb_pad32(int c) { return (c + HB_KC - 1) / HB_KC * HB_KC; }
-inline bool hb_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int s2svc_hifigan_conv1d_dgrad(int dtype, int B, int T, int Cin, int Cout, int k, int dil, const void* dy, const void* w_opT,
@@ -493,39 +392,31 @@ extern "C" int s2svc_hifigan_conv1d_dgrad(int dtype, int B, int T, int Cin, int 
                                           void* stream) {
   S2S_REQUIRE(dtype == S2S_F32 || dtype == S2S_BF16, "hifigan_conv1d_dgrad: dtype 0 (float32) or 1 (bfloat16)");
   S2S_REQUIRE(B >= 1 && T >= 1 && Cin >= 1 && Cin <= 512 && Cout >= 1 && Cout <= 512, "hifigan_conv1d_dgrad: 1 <= C_in, C_out <= 512");
-  S2S_REQUIRE(k >= 1 && k <= 11 && (k & 1) && dil >= 1 && dil <= 5, "hifigan_conv1d_dgrad: k odd <= 11, dil 1..5");
-  S2S_REQUIRE(dy && w_opT && dx && hb_aligned(w_opT), "hifigan_conv1d_dgrad: null pointer or unaligned operand");
-  S2S_REQUIRE((int64_t)B * ((T + HB_BM - 1) / HB_BM) < (1ll << 31), "hifigan_conv1d_dgrad: too many row tiles");
+  S2S_REQUIRE(dy && w_opT && dx && hg_aligned16(w_opT), "hifigan_conv1d_dgrad: null pointer or unaligned operand");
   const int vec = dtype == S2S_F32 ? 4 : 8;
   HbArgs a = {};
+  if (const int rc = hg_conv1d_geom("hifigan_conv1d_dgrad", B, T, k, dil, a.g)) return rc;
   a.a = dy; a.w = w_opT; a.mask = mask_src; a.res = res; a.out = dx;
-  a.La = (int64_t)T * Cout; a.B = B; a.Ka = Cout; a.Kap = hb_pad32(Cout); a.aoff = 0; a.N = Cin; a.ntaps = k;
-  a.tstep = dil; a.toff0 = -((k - 1) / 2) * dil; a.offmin = a.toff0; a.span = (k - 1) * dil;
-  a.Trows = T; a.tiles_per_b = (T + HB_BM - 1) / HB_BM;
+  a.La = (int64_t)T * Cout; a.B = B; a.Ka = Cout; a.Kap = hg_pad32(Cout); a.aoff = 0; a.N = Cin;
   a.slope = slope; a.scale = scale; a.accumulate = accumulate;
-  a.vec_ok = (Cout % vec) == 0 && hb_aligned(dy);
-  return hb_launch(dtype, a, (hipStream_t)stream);
+  a.vec_ok = (Cout % vec) == 0 && hg_aligned16(dy);
+  return hg_launch<HbDgrad>(dtype, a, (hipStream_t)stream);
 }
 
 extern "C" int s2svc_hifigan_tconv1d_dgrad(int dtype, int B, int Tin, int Cin, int Cout, int k, int u, const void* dy, const void* w_opT,
                                            const void* mask_src, float slope, float scale, void* dx, void* stream) {
   S2S_REQUIRE(dtype == S2S_F32 || dtype == S2S_BF16, "hifigan_tconv1d_dgrad: dtype 0 (float32) or 1 (bfloat16)");
   S2S_REQUIRE(B >= 1 && Tin >= 1 && Cin >= 1 && Cin <= 512 && Cout >= 1 && Cout <= 512, "hifigan_tconv1d_dgrad: 1 <= C_in, C_out <= 512");
-  S2S_REQUIRE(u >= 1 && k >= u && ((k - u) & 1) == 0, "hifigan_tconv1d_dgrad: k >= u and (k - u) even");
-  const int ntaps = (k + u - 1) / u, pad = (k - u) / 2;
-  S2S_REQUIRE(ntaps - 1 <= HB_MAXSPAN, "hifigan_tconv1d_dgrad: more than 51 taps per phase");
-  S2S_REQUIRE((int64_t)u * Cout < (1 << 20) && (int64_t)Tin * u < (1ll << 31) / 512, "hifigan_tconv1d_dgrad: u * C_out or output too long");
-  S2S_REQUIRE(dy && w_opT && dx && hb_aligned(w_opT), "hifigan_tconv1d_dgrad: null pointer or unaligned operand");
-  S2S_REQUIRE((int64_t)B * ((Tin + HB_BM - 1) / HB_BM) < (1ll << 31), "hifigan_tconv1d_dgrad: too many row tiles");
+  S2S_REQUIRE((int64_t)u * Cout < (1 << 20), "hifigan_tconv1d_dgrad: u * C_out too large");
+  S2S_REQUIRE(dy && w_opT && dx && hg_aligned16(w_opT), "hifigan_tconv1d_dgrad: null pointer or unaligned operand");
   const int vec = dtype == S2S_F32 ? 4 : 8;
   HbArgs a = {};
+  if (const int rc = hg_tconv1d_geom("hifigan_tconv1d_dgrad", B, Tin, k, u, true, a.g)) return rc;
   a.a = dy; a.w = w_opT; a.mask = mask_src; a.res = nullptr; a.out = dx;
-  a.La = (int64_t)u * Tin * Cout; a.B = B; a.Ka = u * Cout; a.Kap = hb_pad32(u * Cout); a.aoff = pad * Cout; a.N = Cin; a.ntaps = ntaps;
-  a.tstep = 1; a.toff0 = 0; a.offmin = 0; a.span = ntaps - 1;
-  a.Trows = Tin; a.tiles_per_b = (Tin + HB_BM - 1) / HB_BM;
+  a.La = (int64_t)u * Tin * Cout; a.B = B; a.Ka = u * Cout; a.Kap = hg_pad32(u * Cout); a.aoff = a.g.pad * Cout; a.N = Cin;
   a.slope = slope; a.scale = scale; a.accumulate = 0;
-  a.vec_ok = (Cout % vec) == 0 && hb_aligned(dy);          // then u * C_out, pad * C_out and the utterance stride are vector multiples too
-  return hb_launch(dtype, a, (hipStream_t)stream);
+  a.vec_ok = (Cout % vec) == 0 && hg_aligned16(dy);          // then u * C_out, pad * C_out and the utterance stride are vector multiples too
+  return hg_launch<HbDgrad>(dtype, a, (hipStream_t)stream);
 }
 
 // kind 0: Conv1d (dy (B, T, C_out), x (B, T, C_in), u ignored); kind 1: ConvTranspose1d (dy (B, u T, C_out), x (B, T, C_in)).
@@ -541,26 +432,24 @@ extern "C" int s2svc_hifigan_wgrad(int dtype, int kind, int B, int T, int Cin, i
   const int vec = dtype == S2S_F32 ? 4 : 8;
   HwArgs a = {};
   a.dy = dy; a.x = x; a.wpart = wpart; a.bpart = bpart; a.B = B; a.Tin = T; a.Cin = Cin; a.slope = slope; a.chunk = chunk;
+  HgGeom g;
   if (kind == 0) {
-    const int dil = dil_or_u;
-    S2S_REQUIRE(k >= 1 && k <= 11 && (k & 1) && dil >= 1 && dil <= 5, "hifigan_wgrad: Conv1d k odd <= 11, dil 1..5");
-    a.Ldy = (int64_t)T * Cout; a.Na = Cout; a.aoff = 0; a.ntaps = k;
-    a.tstep = dil; a.toff0 = -((k - 1) / 2) * dil; a.offmin = a.toff0; a.span = (k - 1) * dil; a.rows = T;
+    if (const int rc = hg_conv1d_geom("hifigan_wgrad", B, T, k, dil_or_u, g)) return rc;
+    a.Ldy = (int64_t)T * Cout; a.Na = Cout;
   } else {
     const int u = dil_or_u;
-    S2S_REQUIRE(u >= 1 && k >= u && ((k - u) & 1) == 0, "hifigan_wgrad: ConvTranspose1d k >= u and (k - u) even");
-    const int ntaps = (k + u - 1) / u, pad = (k - u) / 2;
-    S2S_REQUIRE(ntaps <= HW_MAXTAPS, "hifigan_wgrad: more than 12 taps per phase");
-    S2S_REQUIRE((int64_t)u * Cout < (1 << 20) && (int64_t)T * u < (1ll << 31) / 512, "hifigan_wgrad: u * C_out or output too long");
-    a.Ldy = (int64_t)u * T * Cout; a.Na = u * Cout; a.aoff = pad * Cout; a.ntaps = ntaps;
-    a.tstep = -1; a.toff0 = 0; a.offmin = -(ntaps - 1); a.span = ntaps - 1; a.rows = T + (pad + u - 1) / u;
+    if (const int rc = hg_tconv1d_geom("hifigan_wgrad", B, T, k, u, false, g)) return rc;
+    S2S_REQUIRE(g.ntaps <= HW_MAXTAPS, "hifigan_wgrad: more than 12 taps per phase");
+    S2S_REQUIRE((int64_t)u * Cout < (1 << 20), "hifigan_wgrad: u * C_out too large");
+    a.Ldy = (int64_t)u * T * Cout; a.Na = u * Cout;
   }
+  a.aoff = g.pad * Cout; a.ntaps = g.ntaps; a.tstep = g.tstep; a.toff0 = g.toff0; a.offmin = g.offmin; a.span = g.span; a.rows = g.rows;
   a.ncpu = (a.rows + chunk - 1) / chunk;
   a.ctiles = (Cin + 31) / 32;
   const int64_t gy = (int64_t)((a.Na + 31) / 32) * a.ctiles;
   S2S_REQUIRE((int64_t)B * a.ncpu < (1ll << 31) && gy <= 65535, "hifigan_wgrad: grid too large");
-  a.vec_dy = (Cout % vec) == 0 && hb_aligned(dy);
-  a.vec_x = (Cin % vec) == 0 && hb_aligned(x);
+  a.vec_dy = (Cout % vec) == 0 && hg_aligned16(dy);
+  a.vec_x = (Cin % vec) == 0 && hg_aligned16(x);
   dim3 grid((unsigned)(B * a.ncpu), (unsigned)gy), block(256);
   if (dtype == S2S_F32) hipLaunchKernelGGL(hifigan_wgrad_kernel<float>, grid, block, 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(hifigan_wgrad_kernel<bf16_t>, grid, block, 0, (hipStream_t)stream, a);
@@ -603,7 +492,7 @@ extern "C" int s2svc_hifigan_fold_bwd(int mode, int D0, int D1, int k, int u, co
   S2S_REQUIRE((mode == 0 || mode == 1) && D0 >= 1 && D1 >= 1 && k >= 1 && u >= 1 && w32 && w_opT, "hifigan_fold_bwd: bad mode / shape or null pointer");
   S2S_REQUIRE(op_dtype == S2S_F32 || op_dtype == S2S_BF16, "hifigan_fold_bwd: operand dtype 0 / 1");
   S2S_REQUIRE(mode != 1 || k >= u, "hifigan_fold_bwd: ConvTranspose1d k >= u");
-  const int Kp = mode == 0 ? hb_pad32(D0) : hb_pad32(u * D1);
+  const int Kp = mode == 0 ? hg_pad32(D0) : hg_pad32(u * D1);
   hipStream_t st = (hipStream_t)stream;
   if (op_dtype == S2S_F32)
     hipLaunchKernelGGL(hifigan_fold_bwd_kernel<float>, dim3(D0), dim3(256), 0, st, mode, D0, D1, k, mode == 1 ? u : 1, Kp, w32, (float*)w_opT);

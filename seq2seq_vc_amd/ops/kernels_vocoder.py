@@ -17,6 +17,19 @@ def _check_act(x, B, T, C, name):
         raise ValueError(f"{name}: contiguous (B, T, C) = {(B, T, C)} expected, got {tuple(x.shape)}")
 
 
+def _out_act(name, out, like, B, T, C, accumulate=False):
+    """The output of a convolution launch: `out` (required when it is accumulated into), or a new tensor in `like`'s dtype; checked to be
+    contiguous (B, T, C) in that dtype -- the kernels store like's element size."""
+    if out is None:
+        if accumulate:
+            raise ValueError(f"{name}: accumulate needs out")
+        out = torch.empty(B, T, C, dtype=like.dtype, device=like.device)
+    _check_act(out, B, T, C, f"{name} out")
+    if out.dtype != like.dtype:
+        raise TypeError(f"{name}: out dtype")
+    return out
+
+
 def hifigan_conv1d(x, w_op, bias, k, dil, cout, slope=0.0, res=None, accumulate=False, scale=1.0, tanh=False, out=None, vlens=None,
                    vmul=1):
     """out = (accumulate ? out : 0) + scale * (conv1d(leaky_relu(x, slope)) + bias (+ res)), optional tanh; x (B, T, C_in)."""
@@ -25,11 +38,7 @@ def hifigan_conv1d(x, w_op, bias, k, dil, cout, slope=0.0, res=None, accumulate=
     _check_act(x, B, T, cin, "hifigan_conv1d x")
     if w_op.dtype != x.dtype or w_op.numel() != cout * k * cin_padded(cin):
         raise ValueError("hifigan_conv1d: operand does not match (C_out, k, C_in padded) in the activation dtype")
-    if out is None:
-        if accumulate:
-            raise ValueError("hifigan_conv1d: accumulate needs out")
-        out = torch.empty(B, T, cout, dtype=x.dtype, device=x.device)
-    _check_act(out, B, T, cout, "hifigan_conv1d out")
+    out = _out_act("hifigan_conv1d", out, x, B, T, cout, accumulate)
     if res is not None:
         _check_act(res, B, T, cout, "hifigan_conv1d res")
         if res.dtype != x.dtype:
@@ -48,9 +57,7 @@ def hifigan_tconv1d(x, w_op, bias, k, u, cout, slope=0.0, out=None, vlens=None, 
     ntaps = (k + u - 1) // u
     if w_op.dtype != x.dtype or w_op.numel() != u * cout * ntaps * cin_padded(cin):
         raise ValueError("hifigan_tconv1d: operand does not match (u C_out, ceil(k / u), C_in padded) in the activation dtype")
-    if out is None:
-        out = torch.empty(B, u * T, cout, dtype=x.dtype, device=x.device)
-    _check_act(out, B, u * T, cout, "hifigan_tconv1d out")
+    out = _out_act("hifigan_tconv1d", out, x, B, u * T, cout)
     _lib.check(_lib.lib().s2svc_hifigan_tconv1d(dt(x), B, T, cin, cout, k, u, ptr(x), ptr(w_op), ptr(bias), float(slope), ptr(out),
                                                 ptr(vlens), int(vmul), stream()), "hifigan_tconv1d")
     return out
@@ -155,13 +162,7 @@ def hifigan_conv1d_dgrad(dy, w_opT, k, dil, cin, mask_src=None, slope=0.0, res=N
     _check_act(dy, B, T, cout, "hifigan_conv1d_dgrad dy")
     if w_opT.dtype != dy.dtype or w_opT.numel() != cin * k * cin_padded(cout) or not w_opT.is_contiguous():
         raise ValueError("hifigan_conv1d_dgrad: operand does not match (C_in, k, C_out padded) in the gradient's dtype")
-    if out is None:
-        if accumulate:
-            raise ValueError("hifigan_conv1d_dgrad: accumulate needs out")
-        out = torch.empty(B, T, cin, dtype=dy.dtype, device=dy.device)
-    _check_act(out, B, T, cin, "hifigan_conv1d_dgrad out")
-    if out.dtype != dy.dtype:
-        raise TypeError("hifigan_conv1d_dgrad: out dtype")
+    out = _out_act("hifigan_conv1d_dgrad", out, dy, B, T, cin, accumulate)
     _check_same("hifigan_conv1d_dgrad mask_src", mask_src, out)
     _check_same("hifigan_conv1d_dgrad res", res, out)
     _lib.check(_lib.lib().s2svc_hifigan_conv1d_dgrad(dt(dy), B, T, cin, cout, k, dil, ptr(dy), ptr(w_opT), ptr(mask_src), float(slope),
@@ -180,11 +181,7 @@ def hifigan_tconv1d_dgrad(dy, w_opT, k, u, cin, mask_src=None, slope=0.0, scale=
     if w_opT.dtype != dy.dtype or w_opT.numel() != cin * ((k + u - 1) // u) * cin_padded(u * cout) or not w_opT.is_contiguous():
         raise ValueError("hifigan_tconv1d_dgrad: operand does not match (C_in, ceil(k / u), u C_out padded) in the gradient's dtype")
     _need_cuda(out)
-    if out is None:
-        out = torch.empty(B, T, cin, dtype=dy.dtype, device=dy.device)
-    _check_act(out, B, T, cin, "hifigan_tconv1d_dgrad out")
-    if out.dtype != dy.dtype:
-        raise TypeError("hifigan_tconv1d_dgrad: out dtype")
+    out = _out_act("hifigan_tconv1d_dgrad", out, dy, B, T, cin)
     _check_same("hifigan_tconv1d_dgrad mask_src", mask_src, out)
     _lib.check(_lib.lib().s2svc_hifigan_tconv1d_dgrad(dt(dy), B, T, cin, cout, k, u, ptr(dy), ptr(w_opT), ptr(mask_src), float(slope),
                                                       float(scale), ptr(out), stream()), "hifigan_tconv1d_dgrad")

@@ -212,13 +212,17 @@ class HifiganGenerator(nn.Module):
             return 1, self.upsample_factors[int(name.split(".")[1])]
         return (2, 1) if name == "conv_post" else (0, 1)
 
+    @staticmethod
+    def _vg(m):
+        """(v, g) fp32 contiguous of a layer in either checkpoint form; g is None without weight norm"""
+        if m.normed:
+            return m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
+        return m.weight.detach().float().contiguous(), None
+
     def _fold(self, name, m, dtype, want_w32=True, want_op=True):
         mode, u = self._layer_mode(name)
         with torch.no_grad():
-            if m.normed:
-                v, g = m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
-            else:
-                v, g = m.weight.detach().float().contiguous(), None
+            v, g = self._vg(m)
             return KV.hifigan_fold(mode, v, g, torch.float32 if dtype is None else dtype, u=u, want_w32=want_w32, want_op=want_op)
 
     def _operands(self, dtype):
@@ -330,10 +334,7 @@ class HifiganGenerator(nn.Module):
         ops, state = {}, {}
         for name, m in self._leaves():
             mode, u = self._layer_mode(name)
-            if m.normed:
-                v, g = m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
-            else:
-                v, g = m.weight.detach().float().contiguous(), None
+            v, g = self._vg(m)
             w32, op = KV.hifigan_fold(mode, v, g, torch.float32, u=u)
             opT = KV.hifigan_fold_bwd(mode, w32, dtype, u=u) if mode != 2 and name != "conv_pre" else None
             ops[name] = (op, m.bias.detach().float().contiguous())
@@ -383,13 +384,17 @@ class HifiganGenerator(nn.Module):
         return result
 
     # ---- execution --------------------------------------------------------------------------------------------------------
-    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None, plan=None, ops=None, keep=None, dtype=None):
+    @staticmethod
+    def _check_input(x, grad_refusal):
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError(grad_refusal)
         if not x.is_cuda:
             raise RuntimeError("HifiganGenerator needs GPU tensors (there is no CPU path)")
-        if torch.is_grad_enabled() and x.requires_grad:
-            raise NotImplementedError("HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("HifiganGenerator input: float32 or bfloat16")
+
+    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None, plan=None, ops=None, keep=None, dtype=None):
+        self._check_input(x, "HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
         dtype = Fn.compute_dtype() if dtype is None else dtype
         if ops is None:
             if self._trainable:                  # an optimiser updates the parameters in place: fold from the live values
@@ -428,12 +433,7 @@ class HifiganGenerator(nn.Module):
             raise ValueError(f"HifiganGenerator: x (B, {self.in_channels}, N) expected, got {tuple(x.shape)}")
         B, _, N = x.shape
         if self._trainable and torch.is_grad_enabled():
-            if x.requires_grad:
-                raise NotImplementedError("HifiganGenerator computes no input gradient: the units / mel are data (detach the input)")
-            if not x.is_cuda:
-                raise RuntimeError("HifiganGenerator needs GPU tensors (there is no CPU path)")
-            if x.dtype not in (torch.float32, torch.bfloat16):
-                raise TypeError("HifiganGenerator input: float32 or bfloat16")
+            self._check_input(x, "HifiganGenerator computes no input gradient: the units / mel are data (detach the input)")
             return _GeneratorFunction.apply(self, x, taps, *[p for _, p in self.named_parameters()])
         y = self._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps)
         return y.view(B, 1, -1)

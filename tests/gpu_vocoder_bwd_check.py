@@ -82,13 +82,9 @@ def _autograd(fn, tensors, dy, amp):
 
 
 # ---- data gradients ---------------------------------------------------------------------------------------------------------
-def dgrad_conv1d_kernel():
-    res = []
-    B, T, cin, cout = 2, 150, 40, 24
-    combos = [(False, False, 1.0, False), (True, False, 1.0, False), (True, True, 1.0, False), (True, True, 1.0 / 3, True),
-              (False, True, 1.0 / 3, False), (False, False, 1.0, True)]
-    g = torch.Generator().manual_seed(11)
-    for k, dil in CONV_PAIRS:
+def _dgrad_conv1d_shape(res, g, cin, cout, pairs, combos):
+    B, T = 2, 150                                            # two row tiles with a ragged edge; the halo lands on both utterance ends
+    for k, dil in pairs:
         w = torch.randn(cout, cin, k, generator=g) / (cin * k) ** 0.5 * 2
         for dtype in (torch.float32, torch.bfloat16):
             m = _away_from_zero((B, cin, T), g).to(dtype)
@@ -113,15 +109,25 @@ def dgrad_conv1d_kernel():
                                               res=_cl(r).to(DEV) if use_res else None, accumulate=acc, scale=scale, out=out)
                 amp = truth(True).to(dtype) if dtype == torch.bfloat16 else None
                 ok, msg = _verdict(dtype, got.transpose(1, 2), truth(False), amp)
-                res.append((ok, f"conv1d dgrad k {k} dil {dil} mask {use_mask} res {use_res} scale {scale:.3f} accumulate {acc}: {msg}"))
+                res.append((ok, f"conv1d dgrad {cout} -> {cin} k {k} dil {dil} mask {use_mask} res {use_res} scale {scale:.3f} accumulate {acc}: {msg}"))
+
+
+def dgrad_conv1d_kernel():
+    """C_in = 40 is the 64-column tile with vector loads of dy in both dtypes.  C_in = 8 / 24 are the 16- and 32-column tiles (the
+    tile body is one template over all three); C_out = 18 makes dy's loads element-wise in both dtypes, C_out = 20 in bf16 only."""
+    res = []
+    combos = [(False, False, 1.0, False), (True, False, 1.0, False), (True, True, 1.0, False), (True, True, 1.0 / 3, True),
+              (False, True, 1.0 / 3, False), (False, False, 1.0, True)]
+    g = torch.Generator().manual_seed(11)
+    _dgrad_conv1d_shape(res, g, 40, 24, CONV_PAIRS, combos)
+    for cin, cout in ((8, 18), (24, 20)):
+        _dgrad_conv1d_shape(res, g, cin, cout, (CONV_PAIRS[0], CONV_PAIRS[-1]), (combos[3], combos[0]))
     return res
 
 
-def dgrad_tconv1d_kernel():
-    res = []
-    B, T, cin, cout = 2, 37, 48, 24
-    g = torch.Generator().manual_seed(12)
-    for k, u in TCONV_PAIRS:
+def _dgrad_tconv1d_shape(res, g, cin, cout, pairs):
+    B, T = 2, 37
+    for k, u in pairs:
         w = torch.randn(cin, cout, k, generator=g) / (cin * k / u) ** 0.5
         for dtype in (torch.float32, torch.bfloat16):
             for use_mask, scale in ((True, 1.0 / 3), (False, 1.0)):
@@ -141,7 +147,18 @@ def dgrad_tconv1d_kernel():
                                                scale=scale, out=_sentinel((B, T, cin), dtype))
                 amp = truth(True).to(dtype) if dtype == torch.bfloat16 else None
                 ok, msg = _verdict(dtype, got.transpose(1, 2), truth(False), amp)
-                res.append((ok, f"tconv1d dgrad k {k} u {u} mask {use_mask} scale {scale:.3f}: {msg}"))
+                res.append((ok, f"tconv1d dgrad {cout} -> {cin} k {k} u {u} mask {use_mask} scale {scale:.3f}: {msg}"))
+
+
+def dgrad_tconv1d_kernel():
+    """The shapes of dgrad_conv1d_kernel for the transposed convolution: C_in = 48 (64 columns, vector loads), then 8 / 24 (16 / 32
+    columns) with C_out = 18 / 20 at the smallest and the largest (k, u)."""
+    res = []
+    g = torch.Generator().manual_seed(12)
+    _dgrad_tconv1d_shape(res, g, 48, 24, TCONV_PAIRS)
+    small, large = min(TCONV_PAIRS), max(TCONV_PAIRS)
+    for cin, cout in ((8, 18), (24, 20)):
+        _dgrad_tconv1d_shape(res, g, cin, cout, (small, large))
     return res
 
 
