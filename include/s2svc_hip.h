@@ -904,6 +904,37 @@ int s2svc_gl_ola(int B, int Tmax, int n_fft, int hop, const float* frames, const
                  void* stream);
 
 /* ========================================================================================== */
+/* Differentiable log-mel spectrogram and its fused L1 loss, fp32, n_fft = 1024                */
+/* (csrc/melspec.hip).  replaces: urhythmic/dataset.py:23-50 (LogMelSpectrogram: reflect pad,  */
+/* torchaudio MelSpectrogram(center=False, power=1), log(clamp(., 1e-5))) and the F.l1_loss    */
+/* behind it in urhythmic_fine_tune_vocoder.py:191-222, forward and backward.                  */
+/* Buffers: wav (B, N) fp32; mel, logmel, tgt, g_logmel (B, n_mels, T) fp32 with               */
+/* T = (N + 2 pad - 1024) / hop + 1 and N > pad; partials [B T] double; frames (B, T, 1024)    */
+/* fp32.  `tables` (8-byte aligned): the Griffin-Lim table for n_fft = 1024.  seg_lo / seg_len */
+/* [n_mels + 1] and wud (513, 2) are the segment form of the mel basis of                      */
+/* s2svc_stft_logmel_fft8, bin_seg [513] the segment of every bin.  No atomics: two calls give */
+/* the same bits and a batch row equals its own B = 1 call.  LIMITS: n_mels <= 128.            */
+/* ========================================================================================== */
+/* 1 where the kernels apply: n_fft = 1024, win_length = n_fft, n_mels <= 128 */
+int s2svc_melspec_supported(int n_fft, int win_length, int nmel);
+/* mel = fb^T |STFT(reflect_pad(wav, pad))| (kept for the backward) and logmel = log(max(mel, eps)), one wavefront per frame.
+   tgt given (partials too, else both NULL): partials[b T + t] = sum_m |logmel - tgt| of frame (b, t), in double. */
+int s2svc_melspec_fwd(int B, int64_t Nw, int T, int hop, int pad, int nmel, const float* wav, const float* tables, const int32_t* seg_lo,
+                      const int32_t* seg_len, const float* wud, float eps, float* mel, float* logmel, const float* tgt, double* partials,
+                      void* stream);
+/* loss[0] = fp32(inv_count * the sum of the n partials in ascending order, in double) */
+int s2svc_melspec_loss_finish(int64_t n, const double* partials, double inv_count, float* loss, void* stream);
+/* frames[b, t, :] = gradient of the windowed frame: the spectrum X is recomputed from wav; g_mel = g / mel where mel >= eps (0 below),
+   g = g_logmel, or (g_logmel = NULL) sign(logmel - tgt) * gscale * gout[0] with sign(0) = 0; G = g_mag X / |X| (0 where |X| = 0);
+   frames = window * Re sum_{k = 0 .. 512} G[k] exp(+2 pi i k n / 1024), interior bins not doubled. */
+int s2svc_melspec_bwd_frames(int B, int64_t Nw, int T, int hop, int pad, int nmel, const float* wav, const float* tables, const float* wud,
+                             const int32_t* bin_seg, float eps, const float* mel, const float* g_logmel, const float* logmel,
+                             const float* tgt, const float* gout, float gscale, float* frames, void* stream);
+/* dwav (B, N): sample j gathers the padded positions pad - j (1 <= j <= pad), j + pad and pad + 2 (N - 1) - j (N - 1 - pad <= j <= N - 2)
+   from the frames that cover each, in ascending (position, frame) order, one lane per sample */
+int s2svc_melspec_bwd_ola(int B, int64_t Nw, int T, int hop, int pad, const float* frames, float* dwav, void* stream);
+
+/* ========================================================================================== */
 /* Urhythmic: segmentation search and time stretcher.                                         */
 /* replaces: urhythmic/segmenter.py:138-191 (_segment / _backtrack, numba-JIT on the host over */
 /* a dense (T, T, K) table, and cluster_merge), urhythmic/stretcher.py:23-71 (F.interpolate    */

@@ -322,6 +322,12 @@ _SIGS = {
     "s2svc_gl_synth": [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
     "s2svc_gl_analyse": [c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_vp, c_vp, c_vp],
     "s2svc_gl_ola": [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "s2svc_melspec_supported": [c_i32, c_i32, c_i32],
+    "s2svc_melspec_fwd": [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "s2svc_melspec_loss_finish": [c_i64, c_vp, ctypes.c_double, c_vp, c_vp],
+    "s2svc_melspec_bwd_frames": [c_i32, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                 c_f32, c_vp, c_vp],
+    "s2svc_melspec_bwd_ola": [c_i32, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp],
     "s2svc_useg_spans": [c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp],
     "s2svc_useg_search": [c_i32, c_i32, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
     "s2svc_useg_stretch": [c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_i32, c_f32, c_vp, c_vp],
