@@ -3,7 +3,7 @@
 // A operand overlap in memory with leading dimension = hop); these kernels do the HBM-bound glue.
 // reference: bin/preprocess.py:30-92 (librosa.stft(center=True, pad_mode="reflect"), abs, mel basis,
 // np.maximum(eps, .), np.log10).
-#include "common.h"
+#include "fft_wave.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
@@ -12,16 +12,7 @@ namespace {
 __global__ void reflect_pad_kernel(int64_t n, int pad, const float* __restrict__ x, float* __restrict__ y) {
   const int64_t m = n + 2 * (int64_t)pad;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t j = i - pad;
-    if (n > 1) {
-      const int64_t period = 2 * (n - 1);
-      j %= period;
-      if (j < 0) j += period;
-      if (j >= n) j = period - j;
-    } else {
-      j = 0;
-    }
-    y[i] = x[j];
+    y[i] = x[reflect_index(i - pad, n, n > 1 ? 2 * (n - 1) : 1)];
   }
 }
 
@@ -99,16 +90,7 @@ __global__ void reflect_pad_batch_kernel(int B, int64_t Nmax, int pad, int64_t l
     const int64_t n = nlen[b];
     float v = 0.f;
     if (n > 0 && i < n + 2 * (int64_t)pad) {
-      int64_t j = i - pad;
-      if (n > 1) {
-        const int64_t period = 2 * (n - 1);
-        j %= period;
-        if (j < 0) j += period;
-        if (j >= n) j = period - j;
-      } else {
-        j = 0;
-      }
-      v = x[(int64_t)b * Nmax + j];
+      v = x[(int64_t)b * Nmax + reflect_index(i - pad, n, n > 1 ? 2 * (n - 1) : 1)];
     }
     y[e] = v;
   }

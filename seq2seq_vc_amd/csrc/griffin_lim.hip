@@ -3,8 +3,8 @@
 //
 //   prepare   one workgroup per (row, frame): optional x * scale + mean, 10^x, the product with the pseudo-inverse of the mel basis,
 //             the clamp (vocoder/griffin_lim.py:20-50) -> S;  X0 = S exp(2 pi i u), u given or drawn from a counter-based generator
-//   synth     one wavefront per frame: inverse real FFT of X[t] in LDS (the radix-4 Stockham passes of stft_fft.hip on the packed
-//             half-size complex sequence), times the window -> frame buffer (B, Tmax, n_fft)
+//   synth     one wavefront per frame: inverse real FFT of X[t] in LDS (fft_wave.h: the Stockham passes on the packed half-size
+//             complex sequence), times the window -> frame buffer (B, Tmax, n_fft)
 //   analyse   one wavefront per frame t: the n_fft samples of the centre-padded waveform that frame t of the forward STFT covers are
 //             GATHERED from the overlapping windowed frames of that buffer in ascending frame order (no atomics: the order of every sum
 //             is fixed, whatever the scheduling or the batch), divided by the squared-window envelope of the frames this row has,
@@ -14,70 +14,15 @@
 //
 // The waveform is materialised once, by ola.  Frames t >= lens[b] are absent (the header's notion): they contribute to no sum, their S / X
 // are written as zero by prepare and nothing else touches them.  A row with fewer than 2 frames has no samples and is absent as a whole.
-// Twiddle factors and the window are one table built on the host in float64 and rounded once:
-//   w_half [H] complex exp(-2 pi i m / H) | w_full [H + 1] complex exp(-2 pi i k / N) | win [N] (zero-padded periodic Hann),  H = N / 2.
-#include "common.h"
+// The transform, its (un)pack steps, the table of twiddle factors and window, the reflect index and the overlap-add frame range are
+// those of fft_wave.h.
+#include "fft_wave.h"
 #include "../../include/s2svc_hip.h"
 #include <float.h>
 
 namespace {
 
-struct c32 { float x, y; };
-__device__ __forceinline__ c32 cadd(c32 a, c32 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ c32 csub(c32 a, c32 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ c32 cmul(c32 a, c32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ c32 mul_mi(c32 a) { return {a.y, -a.x}; }          // a * (-i)
-
 constexpr int WAVES = 4;       // frames per workgroup
-
-// H-point forward complex FFT of one wavefront between its two LDS buffers (Stockham autosort: radix-4 passes and one radix-2 pass
-// if log2(H) is odd); LDS operations of one wavefront execute in order, so a wave barrier between the passes is enough.
-// Returns the buffer that holds the result in natural order; the other one is free.
-template <int H>
-__device__ __forceinline__ c32* fft_forward(c32* src, c32* dst, const c32* tw, int lane) {
-  int p = 1;
-#pragma unroll 1
-  for (; p * 4 <= H; p *= 4) {
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 4;
-    const int st = T / p;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-      const int i = lane + 64 * q;
-      const int k = i & (p - 1);
-      const int j = ((i - k) << 2) + k;
-      const c32 u0 = src[i];
-      c32 u1 = src[i + T], u2 = src[i + 2 * T], u3 = src[i + 3 * T];
-      if (p > 1) {
-        u1 = cmul(u1, tw[k * st]);
-        u2 = cmul(u2, tw[2 * k * st]);
-        u3 = cmul(u3, tw[3 * k * st]);
-      }
-      const c32 v0 = cadd(u0, u2), v1 = csub(u0, u2), v2 = cadd(u1, u3), v3 = mul_mi(csub(u1, u3));
-      dst[j] = cadd(v0, v2);
-      dst[j + p] = cadd(v1, v3);
-      dst[j + 2 * p] = csub(v0, v2);
-      dst[j + 3 * p] = csub(v1, v3);
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  if (p < H) {
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 2;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-      const int i = lane + 64 * q;
-      const int k = i & (p - 1);
-      const int j = ((i - k) << 1) + k;
-      const c32 u0 = src[i], u1 = cmul(src[i + T], tw[k * (T / p)]);
-      dst[j] = cadd(u0, u1);
-      dst[j + p] = csub(u0, u1);
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  __builtin_amdgcn_wave_barrier();
-  return src;
-}
 
 // frames this row has: fewer than two give no sample (n_shift * (T - 1) = 0), the row is absent as a whole
 __device__ __forceinline__ int row_frames(const int32_t* __restrict__ lens, int b, int Tmax) {
@@ -89,13 +34,11 @@ __device__ __forceinline__ int row_frames(const int32_t* __restrict__ lens, int 
 // the windowed frames that cover it, summed in ascending frame order, over the sum of their squared window values where that
 // exceeds the smallest normal fp32 (librosa.istft).  fr = the row's (Tmax, N) windowed frames.
 __device__ __forceinline__ float ola_sample(const float* __restrict__ fr, const float* __restrict__ win, int64_t pos, int T, int hop, int N) {
-  const int64_t lo_num = pos - N + hop;
-  const int t_lo = lo_num > 0 ? (int)(lo_num / hop) : 0;
-  int64_t t_hi = pos / hop;
-  if (t_hi > T - 1) t_hi = T - 1;
+  int t_lo, t_hi;
+  ola_frame_range(pos, N, hop, T, t_lo, t_hi);
   float acc = 0.f, env = 0.f;
-  for (int t = t_lo; t <= (int)t_hi; ++t) {
-    const int o = (int)(pos - (int64_t)t * hop);              // 0 <= o < N by the bounds above
+  for (int t = t_lo; t <= t_hi; ++t) {
+    const int o = (int)(pos - (int64_t)t * hop);              // 0 <= o < N by the range
     const float w = win[o];
     acc += fr[(int64_t)t * N + o];
     env += w * w;
@@ -114,14 +57,6 @@ struct gl_args {
   float* frames;               // (B, Tmax, N)
 };
 
-template <int LOG2N>
-__device__ __forceinline__ void load_twiddles(c32* tw, const float* tables) {
-  constexpr int H = (1 << LOG2N) / 2;
-  const c32* g = reinterpret_cast<const c32*>(tables);
-  for (int i = threadIdx.x; i < H; i += 64 * WAVES) tw[i] = g[i];
-  __syncthreads();
-}
-
 // ---- synth: frames[b, t, :] = win * irfft(X[b, t, :]) ----
 template <int LOG2N>
 __global__ __launch_bounds__(64 * WAVES) void gl_synth_kernel(gl_args a) {
@@ -131,27 +66,22 @@ __global__ __launch_bounds__(64 * WAVES) void gl_synth_kernel(gl_args a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   c32* bx = tw + H + wave * 2 * H;
   c32* by = bx + H;
-  load_twiddles<LOG2N>(tw, a.tables);
-  const c32* tf = reinterpret_cast<const c32*>(a.tables) + H;
-  const float* win = a.tables + 2 * H + 2 * (H + 1);
+  const FftTable tab = fft_table(a.tables, N);
+  load_twiddles<H, 64 * WAVES>(tw, tab);
+  __syncthreads();
   const int gpb = (a.Tmax + WAVES - 1) / WAVES;
 #pragma unroll 1
   for (int g = blockIdx.x; g < a.B * gpb; g += gridDim.x) {
     const int b = g / gpb, t = (g - b * gpb) * WAVES + wave;
     if (t >= row_frames(a.lens, b, a.Tmax)) continue;         // (wave-uniform) absent frame: never read
     const c32* X = reinterpret_cast<const c32*>(a.X) + ((int64_t)b * a.Tmax + t) * (H + 1);
-    // Z[k] = E[k] + i O[k] with E = (X[k] + conj X[H-k]) / 2, O = (X[k] - conj X[H-k]) / 2 * exp(+2 pi i k / N); the imaginary parts of
-    // X[0] and X[H] are ignored (numpy's irfft).  The inverse transform is conj(FFT(conj Z)) / H.
+    // the imaginary parts of X[0] and X[H] are ignored (numpy's irfft)
 #pragma unroll
     for (int q = 0; q < PPL; ++q) {
       const int k = lane + 64 * q;
       c32 xa = X[k], xb = X[H - k];
       if (k == 0) { xa.y = 0.f; xb.y = 0.f; }
-      const c32 xe = {0.5f * (xa.x + xb.x), 0.5f * (xa.y - xb.y)};
-      const c32 d = {0.5f * (xa.x - xb.x), 0.5f * (xa.y + xb.y)};
-      const c32 w = tf[k];
-      const c32 xo = cmul(d, {w.x, -w.y});
-      bx[k] = {xe.x - xo.y, -(xe.y + xo.x)};
+      bx[k] = pack_conj(xa, xb, tab.tf[k]);
     }
     const c32* r = fft_forward<H>(bx, by, tw, lane);
     float* fo = a.frames + ((int64_t)b * a.Tmax + t) * N;
@@ -160,7 +90,7 @@ __global__ __launch_bounds__(64 * WAVES) void gl_synth_kernel(gl_args a) {
     for (int q = 0; q < PPL; ++q) {
       const int n = lane + 64 * q;
       const c32 v = r[n];
-      const float2 wv = *reinterpret_cast<const float2*>(win + 2 * n);
+      const float2 wv = *reinterpret_cast<const float2*>(tab.win + 2 * n);
       *reinterpret_cast<float2*>(fo + 2 * n) = make_float2(v.x * inv * wv.x, -v.y * inv * wv.y);
     }
     __builtin_amdgcn_wave_barrier();
@@ -190,9 +120,9 @@ __global__ __launch_bounds__(64 * WAVES) void gl_analyse_kernel(gl_args a) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   c32* bx = tw + H + wave * 2 * H;
   c32* by = bx + H;
-  load_twiddles<LOG2N>(tw, a.tables);
-  const c32* tf = reinterpret_cast<const c32*>(a.tables) + H;
-  const float* win = a.tables + 2 * H + 2 * (H + 1);
+  const FftTable tab = fft_table(a.tables, N);
+  load_twiddles<H, 64 * WAVES>(tw, tab);
+  __syncthreads();
   const int gpb = (a.Tmax + WAVES - 1) / WAVES;
 #pragma unroll 1
   for (int g = blockIdx.x; g < a.B * gpb; g += gridDim.x) {
@@ -212,37 +142,20 @@ __global__ __launch_bounds__(64 * WAVES) void gl_analyse_kernel(gl_args a) {
         int64_t j = s0 + 2 * p + e;
         bool zero = false;
         if (j < 0 || j >= L) {
-          if (a.reflect) {
-            if (L > 1) {
-              j %= period;
-              if (j < 0) j += period;
-              if (j >= L) j = period - j;
-            } else {
-              j = 0;
-            }
-          } else {
-            zero = true;
-          }
+          if (a.reflect) j = reflect_index(j, L, period);
+          else zero = true;
         }
-        v[e] = zero ? 0.f : ola_sample(fr, win, j + H, T, a.hop, N) * win[2 * p + e];
+        v[e] = zero ? 0.f : ola_sample(fr, tab.win, j + H, T, a.hop, N) * tab.win[2 * p + e];
       }
       bx[p] = {v[0], v[1]};
     }
     const c32* z = fft_forward<H>(bx, by, tw, lane);
-    // X[k] = E + w^k O and X[H - k] = conj(E - w^k O) with E = (Z[k] + conj Z[H-k]) / 2, O = -i (Z[k] - conj Z[H-k]) / 2
     const int64_t row = ((int64_t)b * a.Tmax + t) * (H + 1);
     for (int k = lane; k <= H / 2; k += 64) {
-      const c32 zk = z[k];
-      c32 zc = z[(H - k) & (H - 1)];
-      zc.y = -zc.y;
-      const c32 xe = {0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y)};
-      const c32 xo = mul_mi({0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y)});
-      const c32 wx = cmul(tf[k], xo);
-      project(a, row + k, cadd(xe, wx));
-      if (k != H - k) {
-        const c32 a1 = csub(xe, wx);
-        project(a, row + H - k, {a1.x, -a1.y});
-      }
+      c32 xa, xb;
+      unpack_pair<H>(z, tab.tf, k, xa, xb);
+      project(a, row + k, xa);
+      if (k != H - k) project(a, row + H - k, xb);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -339,19 +252,9 @@ template <int LOG2N>
 int launch_frames(bool analyse, const gl_args& a, hipStream_t st) {
   constexpr int H = (1 << LOG2N) / 2;
   const size_t lds = sizeof(c32) * (H + (size_t)WAVES * 2 * H);
-  const void* fn = analyse ? reinterpret_cast<const void*>(gl_analyse_kernel<LOG2N>) : reinterpret_cast<const void*>(gl_synth_kernel<LOG2N>);
-  static bool attr_set[2] = {false, false};
-  if (lds > 64 * 1024 && !attr_set[analyse]) {
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-      s2svc_set_error("griffin_lim: cannot raise the dynamic LDS limit");
-      return -2;
-    }
-    attr_set[analyse] = true;
-  }
-  const int64_t groups = (int64_t)a.B * ((a.Tmax + WAVES - 1) / WAVES);
-  const int per_cu = (int)(160 * 1024 / lds) > 0 ? (int)(160 * 1024 / lds) : 1;
-  const int64_t resident = 256 * (per_cu < 8 ? per_cu : 8);
-  const dim3 grid((unsigned)(groups < resident ? groups : resident));
+  const char* err = "griffin_lim: cannot raise the dynamic LDS limit";
+  if (int rc = analyse ? fft_raise_lds_limit<gl_analyse_kernel<LOG2N>>(lds, err) : fft_raise_lds_limit<gl_synth_kernel<LOG2N>>(lds, err)) return rc;
+  const dim3 grid = fft_persistent_grid((int64_t)a.B * ((a.Tmax + WAVES - 1) / WAVES), lds, 8);
   if (analyse) hipLaunchKernelGGL(gl_analyse_kernel<LOG2N>, grid, dim3(64 * WAVES), lds, st, a);
   else hipLaunchKernelGGL(gl_synth_kernel<LOG2N>, grid, dim3(64 * WAVES), lds, st, a);
   S2S_CHECK_LAUNCH(analyse ? "gl_analyse_kernel" : "gl_synth_kernel");
@@ -411,9 +314,8 @@ extern "C" int s2svc_gl_ola(int B, int Tmax, int n_fft, int hop, const float* fr
   S2S_REQUIRE(B > 0 && Tmax > 1 && hop > 0 && frames && tables && y, "gl_ola: bad args (Tmax >= 2)");
   const int64_t total = (int64_t)B * hop * (Tmax - 1);
   S2S_REQUIRE((total + 255) / 256 < (1ll << 31), "gl_ola: too many samples for one launch");
-  const float* win = tables + n_fft + (n_fft + 2);
   hipLaunchKernelGGL(gl_ola_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, Tmax, n_fft, hop, frames, lens,
-                     win, y);
+                     fft_table(tables, n_fft).win, y);
   S2S_CHECK_LAUNCH("gl_ola_kernel");
   return 0;
 }

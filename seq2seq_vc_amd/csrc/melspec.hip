@@ -4,89 +4,35 @@
 // scale and norm) -> log(clamp(., 1e-5))) and the F.l1_loss behind it (urhythmic_fine_tune_vocoder.py:191-222), forward and backward.
 //
 //   forward      one wavefront per frame (b, t): windowed load (the reflect padding is index arithmetic on the raw waveform, no padded
-//                copy exists), 512-point complex FFT of the even / odd packed frame in LDS (the radix-4 Stockham passes of
-//                griffin_lim.hip), unpack, magnitude, mel projection by SEGMENTS (stft_fft.hip: a bin has at most two non-zero weights,
-//                in neighbouring filters), mel and log(max(mel, eps)) stored as (B, n_mels, T); with a target also one partial
-//                sum_m |logmel - tgt| per frame, in double
+//                copy exists), 512-point complex FFT of the even / odd packed frame in LDS (fft_wave.h), unpack, magnitude, mel
+//                projection by SEGMENTS (a bin has at most two non-zero weights, in neighbouring filters), mel and
+//                log(max(mel, eps)) stored as (B, n_mels, T); with a target also one partial sum_m |logmel - tgt| per frame, in double
 //   loss finish  the B T partials summed in ascending order in double, scaled, rounded once to fp32
 //   bwd frames   one wavefront per frame: the spectrum is RECOMPUTED from the waveform; g_mel = g_logmel / mel where mel >= eps (ties
 //                included), 0 below; g_mag[k] = the two-weight projection back to the bins; G = g_mag X / |X| (0 where |X| = 0, as
 //                torch.abs of a complex tensor); frame gradient = win[n] Re sum_{k = 0 .. N/2} G[k] exp(+2 pi i k n / N) -- a one-sided
 //                sum, interior bins NOT doubled -- = N irfft(H), H[0] = Re G[0], H[k] = G[k] / 2, H[N/2] = Re G[N/2], by the packed
-//                inverse transform of gl_synth_kernel -> frames (B, T, N)
+//                inverse transform (fft_wave.h: pack_conj) -> frames (B, T, N)
 //   bwd ola      one lane per waveform sample: the up-to-three padded positions that read it (left mirror, itself, right mirror),
 //                each gathered from the frames that cover it, in ascending (position, frame) order -> dwav
 //
 // No atomics: the order of every sum is fixed, whatever the scheduling or the batch, so two calls give the same bits and a batch row
-// equals its own B = 1 call.  Twiddle factors and the window are the table of griffin_lim.hip (built on the host in float64, rounded once).
-#include "common.h"
+// equals its own B = 1 call.  The transform, its (un)pack steps, the table of twiddle factors and window and the overlap-add
+// frame range are those of fft_wave.h.
+#include "fft_wave.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
-
-struct c32 { float x, y; };
-__device__ __forceinline__ c32 cadd(c32 a, c32 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ c32 csub(c32 a, c32 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ c32 cmul(c32 a, c32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ c32 mul_mi(c32 a) { return {a.y, -a.x}; }          // a * (-i)
 
 constexpr int N = 1024, H = N / 2, PPL = H / 64;
 constexpr int WAVES = 4;       // frames per workgroup
 constexpr int WUD_N = 520;     // [H + 1] bin weights, padded
 
-// H-point forward complex FFT of one wavefront between its two LDS buffers (griffin_lim.hip: Stockham autosort, radix-4 passes and one
-// radix-2 pass; LDS operations of one wavefront execute in order, so a wave barrier between the passes is enough).  Returns the
-// buffer that holds the result in natural order; the other one is free.
-__device__ __forceinline__ c32* fft_forward(c32* src, c32* dst, const c32* tw, int lane) {
-  int p = 1;
-#pragma unroll 1
-  for (; p * 4 <= H; p *= 4) {
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 4;
-    const int st = T / p;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-      const int i = lane + 64 * q;
-      const int k = i & (p - 1);
-      const int j = ((i - k) << 2) + k;
-      const c32 u0 = src[i];
-      c32 u1 = src[i + T], u2 = src[i + 2 * T], u3 = src[i + 3 * T];
-      if (p > 1) {
-        u1 = cmul(u1, tw[k * st]);
-        u2 = cmul(u2, tw[2 * k * st]);
-        u3 = cmul(u3, tw[3 * k * st]);
-      }
-      const c32 v0 = cadd(u0, u2), v1 = csub(u0, u2), v2 = cadd(u1, u3), v3 = mul_mi(csub(u1, u3));
-      dst[j] = cadd(v0, v2);
-      dst[j + p] = cadd(v1, v3);
-      dst[j + 2 * p] = csub(v0, v2);
-      dst[j + 3 * p] = csub(v1, v3);
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  {                                                           // 512 = 4^4 * 2: one radix-2 pass left (p = H / 2)
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 2;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-      const int i = lane + 64 * q;
-      const int k = i & (p - 1);
-      const int j = ((i - k) << 1) + k;
-      const c32 u0 = src[i], u1 = cmul(src[i + T], tw[k * (T / p)]);
-      dst[j] = cadd(u0, u1);
-      dst[j + p] = csub(u0, u1);
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  __builtin_amdgcn_wave_barrier();
-  return src;
-}
-
 struct mel_args {
   int B, T, hop, pad, nmel;
   int64_t Nw;                  // samples of every row
   const float* wav;            // (B, Nw)
-  const float* tables;         // w_half [H] complex | w_full [H + 1] complex | win [N]
+  const float* tables;         // the packed table of fft_wave.h
   const int32_t* seg_lo;       // [nmel + 1] first bin of segment s: the bins between the peaks of filters s - 1 and s
   const int32_t* seg_len;      // [nmel + 1]
   const float* wud;            // [H + 1][2]: weight of filter s(k) (rising side) and of filter s(k) - 1 (falling side) at bin k
@@ -131,9 +77,8 @@ __device__ __forceinline__ lds_view carve(unsigned char* smem, const mel_args& a
   return v;
 }
 
-__device__ __forceinline__ void load_tables(const lds_view& v, const mel_args& a) {
-  const c32* g = reinterpret_cast<const c32*>(a.tables);
-  for (int i = threadIdx.x; i < H; i += 64 * WAVES) v.tw[i] = g[i];
+__device__ __forceinline__ void load_tables(const lds_view& v, const mel_args& a, const FftTable& tab) {
+  load_twiddles<H, 64 * WAVES>(v.tw, tab);
   for (int i = threadIdx.x; i < H + 1; i += 64 * WAVES) {
     v.wud[i] = reinterpret_cast<const float2*>(a.wud)[i];
     if (a.bin_seg) {
@@ -174,28 +119,13 @@ __device__ __forceinline__ void load_frame(const mel_args& a, int b, int t, c32*
   }
 }
 
-// X[k] and X[H - k] of the real frame from the packed transform Z: X[k] = E + w^k O, X[H - k] = conj(E - w^k O) with
-// E = (Z[k] + conj Z[H-k]) / 2, O = -i (Z[k] - conj Z[H-k]) / 2.  k = 0 gives X[0] and X[N/2] (both real).
-__device__ __forceinline__ void unpack_pair(const c32* z, const c32* tf, int k, c32& xa, c32& xb) {
-  const c32 zk = z[k];
-  c32 zc = z[(H - k) & (H - 1)];
-  zc.y = -zc.y;
-  const c32 xe = {0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y)};
-  const c32 xo = mul_mi({0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y)});
-  const c32 wx = cmul(tf[k], xo);
-  xa = cadd(xe, wx);
-  const c32 a1 = csub(xe, wx);
-  xb = {a1.x, -a1.y};
-}
-
 // ---- forward ----
 __global__ __launch_bounds__(64 * WAVES) void melspec_fwd_kernel(mel_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const lds_view v = carve(smem_raw, a, wave);
-  load_tables(v, a);
-  const c32* tf = reinterpret_cast<const c32*>(a.tables) + H;
-  const float* win = a.tables + 2 * H + 2 * (H + 1);
+  const FftTable tab = fft_table(a.tables, N);
+  load_tables(v, a, tab);
   const int nseg = a.nmel + 1;
   float* up = v.row;
   float* dn = up + nseg;
@@ -204,12 +134,12 @@ __global__ __launch_bounds__(64 * WAVES) void melspec_fwd_kernel(mel_args a) {
   for (int g = blockIdx.x; g < a.B * gpb; g += gridDim.x) {
     const int b = g / gpb, t = (g - b * gpb) * WAVES + wave;
     if (t >= a.T) continue;                                   // (wave-uniform)
-    load_frame(a, b, t, v.bx, win, lane);
-    c32* z = fft_forward(v.bx, v.by, v.tw, lane);
+    load_frame(a, b, t, v.bx, tab.win, lane);
+    c32* z = fft_forward<H>(v.bx, v.by, v.tw, lane);
     float* mag = reinterpret_cast<float*>(z == v.bx ? v.by : v.bx);      // [H + 1] <= 2 H floats
     for (int k = lane; k <= H / 2; k += 64) {
       c32 xa, xb;
-      unpack_pair(z, tf, k, xa, xb);
+      unpack_pair<H>(z, tab.tf, k, xa, xb);
       mag[k] = sqrtf(xa.x * xa.x + xa.y * xa.y);
       mag[H - k] = sqrtf(xb.x * xb.x + xb.y * xb.y);
     }
@@ -264,23 +194,13 @@ __global__ __launch_bounds__(256) void melspec_loss_finish_kernel(int64_t n, con
   if (threadIdx.x == 0) loss[0] = (float)(acc * inv_count);
 }
 
-// conj of the packed inverse-transform input Z[k] = E + i O, E = (xa + conj xb) / 2, O = (xa - conj xb) / 2 * exp(+2 pi i k / N),
-// for the pair xa = Y[k], xb = Y[H - k] of a one-sided spectrum Y (gl_synth_kernel); w = exp(-2 pi i k / N)
-__device__ __forceinline__ c32 pack_conj(c32 xa, c32 xb, c32 w) {
-  const c32 xe = {0.5f * (xa.x + xb.x), 0.5f * (xa.y - xb.y)};
-  const c32 d = {0.5f * (xa.x - xb.x), 0.5f * (xa.y + xb.y)};
-  const c32 xo = cmul(d, {w.x, -w.y});
-  return {xe.x - xo.y, -(xe.y + xo.x)};
-}
-
 // ---- backward, launch 1: frames[b, t, :] = the gradient of the windowed frame ----
 __global__ __launch_bounds__(64 * WAVES) void melspec_bwd_frames_kernel(mel_args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const lds_view v = carve(smem_raw, a, wave);
-  load_tables(v, a);
-  const c32* tf = reinterpret_cast<const c32*>(a.tables) + H;
-  const float* win = a.tables + 2 * H + 2 * (H + 1);
+  const FftTable tab = fft_table(a.tables, N);
+  load_tables(v, a, tab);
   float* gm = v.row;                                          // [nmel] gradient of the linear mel
   const float gs = a.g_logmel ? 0.f : a.gscale * a.gout[0];
   const int gpb = (a.T + WAVES - 1) / WAVES;
@@ -311,29 +231,29 @@ __global__ __launch_bounds__(64 * WAVES) void melspec_bwd_frames_kernel(mel_args
       }
       gm[m] = ml >= a.eps ? gl / ml : 0.f;                    // clamp(min = eps): the gradient passes at a tie
     }
-    load_frame(a, b, t, v.bx, win, lane);
-    c32* z = fft_forward(v.bx, v.by, v.tw, lane);
+    load_frame(a, b, t, v.bx, tab.win, lane);
+    c32* z = fft_forward<H>(v.bx, v.by, v.tw, lane);
     c32* y = z == v.bx ? v.by : v.bx;
     for (int k = lane; k <= H / 2; k += 64) {
       c32 xa, xb;
-      unpack_pair(z, tf, k, xa, xb);
+      unpack_pair<H>(z, tab.tf, k, xa, xb);
       const c32 ga = grad_bin(xa, k), gb = grad_bin(xb, H - k);
       if (k == 0) {                                           // bins 0 and N/2: real parts, not halved
-        y[0] = pack_conj({2.f * ga.x, 0.f}, {2.f * gb.x, 0.f}, tf[0]);
+        y[0] = pack_conj({2.f * ga.x, 0.f}, {2.f * gb.x, 0.f}, tab.tf[0]);
       } else if (k == H / 2) {
-        y[k] = pack_conj(ga, ga, tf[k]);
+        y[k] = pack_conj(ga, ga, tab.tf[k]);
       } else {
-        y[k] = pack_conj(ga, gb, tf[k]);
-        y[H - k] = pack_conj(gb, ga, tf[H - k]);
+        y[k] = pack_conj(ga, gb, tab.tf[k]);
+        y[H - k] = pack_conj(gb, ga, tab.tf[H - k]);
       }
     }
-    const c32* r = fft_forward(y, z, v.tw, lane);
+    const c32* r = fft_forward<H>(y, z, v.tw, lane);
     float* fo = a.frames + ((int64_t)b * a.T + t) * N;
 #pragma unroll
     for (int q = 0; q < PPL; ++q) {
       const int n = lane + 64 * q;
       const c32 rv = r[n];
-      const float2 wv = *reinterpret_cast<const float2*>(win + 2 * n);
+      const float2 wv = *reinterpret_cast<const float2*>(tab.win + 2 * n);
       *reinterpret_cast<float2*>(fo + 2 * n) = make_float2(rv.x * wv.x, -rv.y * wv.y);
     }
     __builtin_amdgcn_wave_barrier();
@@ -358,11 +278,9 @@ __global__ __launch_bounds__(256) void melspec_bwd_ola_kernel(int B, int64_t Nw,
   float acc = 0.f;
   for (int q = 0; q < np; ++q) {
     const int64_t p = pos[q];
-    const int64_t lo_num = p - N + hop;
-    const int t_lo = lo_num > 0 ? (int)(lo_num / hop) : 0;    // ceil((p - N + 1) / hop)
-    int64_t t_hi = p / hop;
-    if (t_hi > T - 1) t_hi = T - 1;
-    for (int t = t_lo; t <= (int)t_hi; ++t) acc += fr[(int64_t)t * N + (p - (int64_t)t * hop)];     // 0 <= p - t hop < N by the bounds
+    int t_lo, t_hi;
+    ola_frame_range(p, N, hop, T, t_lo, t_hi);
+    for (int t = t_lo; t <= t_hi; ++t) acc += fr[(int64_t)t * N + (p - (int64_t)t * hop)];     // 0 <= p - t hop < N by the range
   }
   dwav[i] = acc;
 }
@@ -373,10 +291,9 @@ bool geometry_ok(int B, int64_t Nw, int T, int hop, int pad, int nmel) {
 }
 
 int launch_frames(bool bwd, const mel_args& a, hipStream_t st) {
-  const size_t lds = lds_bytes(a.nmel);                       // < 64 KB for n_mels <= 128
-  const int64_t groups = (int64_t)a.B * ((a.T + WAVES - 1) / WAVES);
-  const int64_t resident = 256 * 3;
-  const dim3 grid((unsigned)(groups < resident ? groups : resident));
+  const size_t lds = lds_bytes(a.nmel);                       // 46 - 48 KB for n_mels <= 128: no limit to raise, three per CU
+  S2S_REQUIRE(lds <= 64 * 1024 && fft_resident_groups(lds, 3) == 256 * 3, "melspec: the LDS layout no longer fits three workgroups per CU");
+  const dim3 grid = fft_persistent_grid((int64_t)a.B * ((a.T + WAVES - 1) / WAVES), lds, 3);
   if (bwd) hipLaunchKernelGGL(melspec_bwd_frames_kernel, grid, dim3(64 * WAVES), lds, st, a);
   else hipLaunchKernelGGL(melspec_fwd_kernel, grid, dim3(64 * WAVES), lds, st, a);
   S2S_CHECK_LAUNCH(bwd ? "melspec_bwd_frames_kernel" : "melspec_fwd_kernel");

@@ -12,17 +12,13 @@
 // normalised and stored as one coalesced row of n_mels floats.  HBM traffic per frame = hop samples in (the overlap is served
 // by the L2) + n_mels floats out: the algorithmic minimum (4 B / sample + 320 B / frame); the DFT-as-GEMM formulation it
 // replaces (frontend.hip) did 40x the flops and wrote / re-read a (frames, N + 2) fp32 spectrum.
-// Twiddle factors, window and mel weights are tables built on the host in float64 and rounded once.
-#include "common.h"
+// Twiddle factors, window and mel weights are tables built on the host in float64 and rounded once.  The transform, its unpack step,
+// the view of the table and the reflect index are those of fft_wave.h.
+#include "fft_wave.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
 
-struct c32 { float x, y; };
-__device__ __forceinline__ c32 cadd(c32 a, c32 b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ c32 csub(c32 a, c32 b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ c32 cmul(c32 a, c32 b) { return {a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ c32 mul_mi(c32 a) { return {a.y, -a.x}; }          // a * (-i)
 // (padding the FFT buffers against the bank conflicts of the first passes' strided stores -- one element per 32 -- was measured:
 // 80 -> 82.5 KB of LDS per workgroup drops the occupancy from two workgroups per CU to one and costs more than it saves)
 
@@ -32,10 +28,8 @@ struct fft_args {
   const float* x;              // (B, Nmax) raw waveforms
   const int32_t* nlen;         // (B) samples
   const int32_t* frames;       // (B) frames = 1 + n // hop
-  const float* tables;         // packed fp32, 16-byte aligned, zero-filled to whole 16-byte vectors:
-                               //   w_half [N/2] complex exp(-2 pi i m / (N/2)) | w_full [N/2 + 1] complex exp(-2 pi i k / N) |
-                               //   win [N] (zero-padded window) | melw [melw_n rounded up to even] (compact mel weights: filter m =
-                               //   melw[off[m] .. off[m] + hi[m] - lo[m]))
+  const float* tables;         // packed fp32, 16-byte aligned, zero-filled to whole 16-byte vectors: the table of fft_wave.h |
+                               //   melw [melw_n rounded up to even] (compact mel weights: filter m = melw[off[m] .. off[m] + hi[m] - lo[m]))
   const int32_t* mel_lo;
   const int32_t* mel_hi;
   const int32_t* mel_off;
@@ -48,16 +42,24 @@ struct fft_args {
 
 constexpr int WAVES = 8;       // frames per workgroup
 
+// bytes of the packed table with its mel weights, in whole 16-byte vectors
+inline __host__ __device__ size_t table_bytes(int N, int melw_n) {
+  return (sizeof(float) * (fft_table_floats(N) + ((melw_n + 1) & ~1)) + 15) / 16 * 16;
+}
+// the compact mel weights [melw_n]: they follow the window, without a pad
+__device__ __forceinline__ const float* mel_weights(const FftTable& tab, int N) { return tab.win + N; }
+
 // LOG2N = log2(fft size): 9, 10, 11
 template <int LOG2N>
 __global__ __launch_bounds__(64 * WAVES) void stft_logmel_fft_kernel(fft_args a) {
   constexpr int N = 1 << LOG2N, H = N / 2, PPL = H / 64;      // points of the complex FFT, points per lane
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  c32* tw = reinterpret_cast<c32*>(smem_raw);                 // [H] twiddles of the H-point FFT
-  c32* tf = tw + H;                                           // [H + 1] unpack twiddles
-  float* win = reinterpret_cast<float*>(tf + H + 1);          // [N]
-  float* mw = win + N;                                        // [melw_n]
-  const int tab_vecs = (int)((sizeof(c32) * (2 * H + 1) + sizeof(float) * (N + ((a.melw_n + 1) & ~1)) + 15) / 16);
+  const FftTable tab = fft_table(reinterpret_cast<const float*>(smem_raw), N);      // the whole table lies in LDS
+  const c32* tw = tab.tw;
+  const c32* tf = tab.tf;
+  const float* win = tab.win;
+  const float* mw = mel_weights(tab, N);
+  const int tab_vecs = (int)(table_bytes(N, a.melw_n) / 16);
   c32* bufs = reinterpret_cast<c32*>(smem_raw + (size_t)tab_vecs * 16);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   c32* bx = bufs + wave * 2 * H;
@@ -116,79 +118,19 @@ __global__ __launch_bounds__(64 * WAVES) void stft_logmel_fft_kernel(fft_args a)
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         int64_t j = s0 + 2 * p + e;
-        if (!inner) {
-          if (n > 1) {
-            j %= period;
-            if (j < 0) j += period;
-            if (j >= n) j = period - j;
-          } else {
-            j = 0;
-          }
-        }
+        if (!inner) j = reflect_index(j, n, period);
         v[e] = xb[j] * win[2 * p + e];
       }
       bx[p] = {v[0], v[1]};
     }
   }
-  // ---- H-point complex FFT, Stockham autosort: radix-4 passes (p = 1, 4, 16, ...) and one radix-2 pass if log2(H) is odd ----
-  c32* src = bx;
-  c32* dst = by;
-  int p = 1;
-#pragma unroll 1
-  for (; p * 4 <= H; p *= 4) {
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 4;                                  // butterflies per pass
-#pragma unroll
-    for (int q = 0; q < (T + 63) / 64; ++q) {
-      const int i = lane + 64 * q;
-      if (T % 64 == 0 || i < T) {
-        const int k = i & (p - 1);
-        const int j = ((i - k) << 2) + k;
-        // twiddles exp(-2 pi i k r / (4 p)), r = 1, 2, 3 = table entries k r (H / (4 p))
-        const int st = (H / 4) / p;
-        const c32 u0 = src[i];
-        c32 u1 = src[i + T], u2 = src[i + 2 * T], u3 = src[i + 3 * T];
-        if (p > 1) {                                         // (uniform) the first pass has k = 0: all twiddles are 1
-          u1 = cmul(u1, tw[k * st]);
-          u2 = cmul(u2, tw[2 * k * st]);
-          u3 = cmul(u3, tw[3 * k * st]);
-        }
-        const c32 v0 = cadd(u0, u2), v1 = csub(u0, u2), v2 = cadd(u1, u3), v3 = mul_mi(csub(u1, u3));
-        dst[j] = cadd(v0, v2);
-        dst[j + p] = cadd(v1, v3);
-        dst[j + 2 * p] = csub(v0, v2);
-        dst[j + 3 * p] = csub(v1, v3);
-      }
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  if (p < H) {                                                // one radix-2 pass left (p = H / 2)
-    __builtin_amdgcn_wave_barrier();
-    constexpr int T = H / 2;
-#pragma unroll
-    for (int q = 0; q < T / 64; ++q) {
-      const int i = lane + 64 * q;
-      const int k = i & (p - 1);
-      const int j = ((i - k) << 1) + k;
-      const c32 u0 = src[i], u1 = cmul(src[i + T], tw[k * ((H / 2) / p)]);
-      dst[j] = cadd(u0, u1);
-      dst[j + p] = csub(u0, u1);
-    }
-    c32* tmp = src; src = dst; dst = tmp;
-  }
-  __builtin_amdgcn_wave_barrier();
+  // ---- H-point complex FFT ----
+  const c32* z = fft_forward<H>(bx, by, tw, lane);
   // ---- unpack to the one-sided spectrum of the real frame, magnitudes into the free buffer ----
-  float* mag = reinterpret_cast<float*>(dst);                 // [H + 1] <= 2 H floats
-  // X[k] = xe + w^k xo and X[H - k] = conj(xe - w^k xo) with xe = (Z[k] + conj Z[H-k]) / 2, xo = -i (Z[k] - conj Z[H-k]) / 2:
-  // one twiddle product gives the magnitudes of two bins
+  float* mag = reinterpret_cast<float*>(z == bx ? by : bx);   // [H + 1] <= 2 H floats
   for (int k = lane; k <= H / 2; k += 64) {
-    const c32 zk = src[k];
-    c32 zc = src[(H - k) & (H - 1)];
-    zc.y = -zc.y;
-    const c32 xe = {0.5f * (zk.x + zc.x), 0.5f * (zk.y + zc.y)};
-    const c32 xo = mul_mi({0.5f * (zk.x - zc.x), 0.5f * (zk.y - zc.y)});
-    const c32 wx = cmul(tf[k], xo);
-    const c32 a0 = cadd(xe, wx), a1 = csub(xe, wx);
+    c32 a0, a1;
+    unpack_pair<H>(z, tf, k, a0, a1);
     mag[k] = sqrtf(a0.x * a0.x + a0.y * a0.y);
     mag[H - k] = sqrtf(a1.x * a1.x + a1.y * a1.y);
   }
@@ -221,18 +163,10 @@ __global__ __launch_bounds__(64 * WAVES) void stft_logmel_fft_kernel(fft_args a)
 template <int LOG2N>
 int launch(const fft_args& a, hipStream_t st) {
   constexpr int N = 1 << LOG2N, H = N / 2;
-  const size_t tab = (sizeof(c32) * (2 * H + 1) + sizeof(float) * (N + ((a.melw_n + 1) & ~1)) + 15) / 16 * 16;
-  const size_t lds = tab + sizeof(c32) * WAVES * 2 * H;
-  static size_t attr_set = 0;
-  if (lds > 64 * 1024 && attr_set < lds) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_logmel_fft_kernel<LOG2N>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess) { s2svc_set_error("stft_logmel_fft: cannot raise the dynamic LDS limit"); return -2; }
-    attr_set = lds;
-  }
-  const int groups = a.B * ((a.Tmax + WAVES - 1) / WAVES);
-  const int per_cu = (int)(160 * 1024 / lds) > 0 ? (int)(160 * 1024 / lds) : 1;
-  const int resident = 256 * (per_cu < 4 ? per_cu : 4);       // workgroups the chip holds at once
-  hipLaunchKernelGGL(stft_logmel_fft_kernel<LOG2N>, dim3(groups < resident ? groups : resident), dim3(64 * WAVES), lds, st, a);
+  const size_t lds = table_bytes(N, a.melw_n) + sizeof(c32) * WAVES * 2 * H;
+  if (int rc = fft_raise_lds_limit<stft_logmel_fft_kernel<LOG2N>>(lds, "stft_logmel_fft: cannot raise the dynamic LDS limit")) return rc;
+  const dim3 grid = fft_persistent_grid(a.B * ((a.Tmax + WAVES - 1) / WAVES), lds, 4);
+  hipLaunchKernelGGL(stft_logmel_fft_kernel<LOG2N>, grid, dim3(64 * WAVES), lds, st, a);
   S2S_CHECK_LAUNCH("stft_logmel_fft_kernel");
   return 0;
 }
@@ -257,7 +191,7 @@ struct fft8_args {
   const float* x;
   const int32_t* nlen;
   const int32_t* frames;
-  const float* tables;         // the packed table of the generic kernel: w_half [512] complex | w_full [513] complex | win [1024] | ...
+  const float* tables;         // the packed table of the generic kernel
   const int32_t* seg_lo;       // [nmel + 1] first bin of segment s: the bins between the peaks of filters s - 1 and s
   const int32_t* seg_len;      // [nmel + 1]
   const float* wud;            // [513][2]: weight of filter s(k) (rising side) and of filter s(k) - 1 (falling side) at bin k
@@ -306,9 +240,10 @@ __global__ __launch_bounds__(64 * WAVES8) __attribute__((amdgpu_waves_per_eu(3, 
   for (int i = threadIdx.x; i < H + 1; i += 64 * WAVES8) wud[i] = reinterpret_cast<const float2*>(a.wud)[i];
   for (int i = threadIdx.x; i < nseg; i += 64 * WAVES8) { seg_lo[i] = a.seg_lo[i]; seg_len[i] = a.seg_len[i]; }
   // per-lane constants
-  const c32* w_half = reinterpret_cast<const c32*>(a.tables);
-  const c32* w_full = w_half + H;
-  const float* wing = reinterpret_cast<const float*>(w_full + H + 1);
+  const FftTable tab = fft_table(a.tables, N);
+  const c32* w_half = tab.tw;
+  const c32* w_full = tab.tf;
+  const float* wing = tab.win;
   float2 wn[8];
   c32 tw2[7], tw3[7], tf[8];
 #pragma unroll
@@ -354,15 +289,7 @@ __global__ __launch_bounds__(64 * WAVES8) __attribute__((amdgpu_waves_per_eu(3, 
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           int64_t j = s0 + 2 * (lane + 64 * q) + e;
-          if (!inner) {
-            if (n > 1) {
-              j %= period;
-              if (j < 0) j += period;
-              if (j >= n) j = period - j;
-            } else {
-              j = 0;
-            }
-          }
+          if (!inner) j = reflect_index(j, n, period);
           v[e] = xb[j];
         }
         xv[q] = make_float2(v[0], v[1]);
@@ -428,6 +355,7 @@ __global__ __launch_bounds__(64 * WAVES8) __attribute__((amdgpu_waves_per_eu(3, 
     for (int r = 0; r < 8; ++r) bx[pad8(lane + 64 * r)] = u[r];
     __builtin_amdgcn_wave_barrier();
     float* mag = reinterpret_cast<float*>(by);               // [H + 1]
+    // fft_wave.h's unpack_pair in register form: Z[k] is the lane's own, only X[k] of the pair is formed (the partner lane forms X[H - k])
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
       const int k = lane + 64 * r;
@@ -504,16 +432,9 @@ extern "C" int s2svc_stft_logmel_fft8(int B, int64_t Nmax, int Tmax, int hop, in
   a.out = out;
   const int updn_n = (2 * (nmel + 1) + 3) & ~3;
   const size_t lds = 520 * 8 + (size_t)(nmel + 1) * 8 + (size_t)WAVES8 * updn_n * 4 + (size_t)WAVES8 * 2 * 576 * 8;
-  static size_t attr_set = 0;
-  if (lds > 64 * 1024 && attr_set < lds) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(stft_logmel_fft8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-        hipSuccess) { s2svc_set_error("stft_logmel_fft8: cannot raise the dynamic LDS limit"); return -2; }
-    attr_set = lds;
-  }
-  const int groups = B * ((Tmax + WAVES8 - 1) / WAVES8);
-  const int per_cu = (int)(160 * 1024 / lds) > 0 ? (int)(160 * 1024 / lds) : 1;
-  const int resident = 256 * (per_cu < 3 ? per_cu : 3);
-  hipLaunchKernelGGL(stft_logmel_fft8_kernel, dim3(groups < resident ? groups : resident), dim3(64 * WAVES8), lds, (hipStream_t)stream, a);
+  if (int rc = fft_raise_lds_limit<stft_logmel_fft8_kernel>(lds, "stft_logmel_fft8: cannot raise the dynamic LDS limit")) return rc;
+  const dim3 grid = fft_persistent_grid(B * ((Tmax + WAVES8 - 1) / WAVES8), lds, 3);
+  hipLaunchKernelGGL(stft_logmel_fft8_kernel, grid, dim3(64 * WAVES8), lds, (hipStream_t)stream, a);
   S2S_CHECK_LAUNCH("stft_logmel_fft8_kernel");
   return 0;
 }

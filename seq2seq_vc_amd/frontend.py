@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from .ops import kernels as K
+from .ops.fft_tables import hann_padded, pad_vec4, packed_table, segment_tables
 
 _BASIS = {}
 
@@ -55,12 +56,7 @@ def mel_basis(sr, n_fft, n_mels, fmin, fmax):
 
 def dft_basis(n_fft, win_length=None):
     """Windowed one-sided DFT basis rows [w*cos ; -w*sin] -> (2*(n_fft//2+1), n_fft) float32."""
-    win_length = n_fft if win_length is None else win_length
-    k = np.arange(win_length)
-    win = 0.5 - 0.5 * np.cos(2 * np.pi * k / win_length)         # periodic Hann (fftbins=True)
-    lp = (n_fft - win_length) // 2
-    w = np.zeros(n_fft)
-    w[lp:lp + win_length] = win
+    w = hann_padded(n_fft, win_length)                           # periodic Hann (fftbins=True)
     n = np.arange(n_fft // 2 + 1)[:, None]
     ang = 2 * np.pi * n * np.arange(n_fft)[None, :] / n_fft
     return np.concatenate([np.cos(ang) * w, -np.sin(ang) * w], axis=0).astype(np.float32)
@@ -148,19 +144,10 @@ _FFT_TABLES = {}
 
 
 def _fft_tables(device, sr, n_fft, win_length, n_mels, fmin, fmax):
-    """Tables of the FFT-in-LDS kernel (csrc/stft_fft.hip), built in float64 and rounded once: window (zero-padded to n_fft),
-    twiddles of the n_fft/2-point FFT and of the real-FFT unpack step, the mel filters' non-zero weights back to back."""
+    """Tables of the FFT-in-LDS kernel (csrc/stft_fft.hip), built in float64 and rounded once: the packed twiddle and window table
+    (ops/fft_tables.py) with the mel filters' non-zero weights back to back behind it."""
     key = (str(device), sr, n_fft, win_length, n_mels, fmin, fmax)
     if key not in _FFT_TABLES:
-        wl = n_fft if win_length is None else win_length
-        win = np.zeros(n_fft)
-        lp = (n_fft - wl) // 2
-        win[lp:lp + wl] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(wl) / wl)
-        h = n_fft // 2
-        a = -2 * np.pi * np.arange(h) / h
-        w_half = np.stack([np.cos(a), np.sin(a)], 1)
-        a = -2 * np.pi * np.arange(h + 1) / n_fft
-        w_full = np.stack([np.cos(a), np.sin(a)], 1)
         melb = mel_basis(sr, n_fft, n_mels, fmin, fmax)
         lo, hi = _mel_ranges(melb)
         off = np.concatenate([[0], np.cumsum(hi - lo)]).astype(np.int32)
@@ -168,8 +155,7 @@ def _fft_tables(device, sr, n_fft, win_length, n_mels, fmin, fmax):
         melw = np.concatenate([melb[m, lo[m]:hi[m]] for m in range(n_mels)] + [np.zeros(maxw + 2, np.float32)]).astype(np.float32)
         t = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x.astype(dt))).to(device)
         melw_n = int(len(melw))
-        packed = np.concatenate([w_half.reshape(-1), w_full.reshape(-1), win, melw, np.zeros(melw_n % 2)]).astype(np.float32)
-        packed = np.concatenate([packed, np.zeros((-len(packed)) % 4, np.float32)])           # whole 16-byte vectors
+        packed = pad_vec4(np.concatenate([packed_table(n_fft, win_length), melw, np.zeros(melw_n % 2, np.float32)]))
         _FFT_TABLES[key] = (t(packed, np.float32), t(lo, np.int32), t(hi, np.int32), t(off[:-1], np.int32), melw_n, maxw)
     return _FFT_TABLES[key]
 
@@ -178,51 +164,12 @@ _FFT8_TABLES = {}
 
 
 def _fft8_tables(device, sr, n_fft, n_mels, fmin, fmax):
-    """Segment form of the mel basis for the radix-8 kernel (s2svc_stft_logmel_fft8), or None if the basis does not have the
-    structure it needs: every bin has at most two non-zero weights, in neighbouring filters (true for librosa's triangular
-    filters).  Segment s (0 .. n_mels) = the bins between the peaks of filters s - 1 and s: rising side of filter s (weight
-    wud[k][0]), falling side of filter s - 1 (wud[k][1]); mel[m] = sum over segment m of wud[:, 0] |X| + sum over segment m + 1 of
-    wud[:, 1] |X|.  -> (seg_lo, seg_len (n_mels + 1), wud (bins, 2))."""
+    """Segment form of the mel basis for the radix-8 kernel (s2svc_stft_logmel_fft8): (seg_lo, seg_len, wud) of
+    ops/fft_tables.segment_tables, or None if n_fft or the basis is not what the kernel needs."""
     key = (str(device), sr, n_fft, n_mels, fmin, fmax)
     if key not in _FFT8_TABLES:
-        melb = np.asarray(mel_basis(sr, n_fft, n_mels, fmin, fmax), dtype=np.float32)
-        nb = melb.shape[1]
-        peak = melb.argmax(axis=1)
-        seg = np.full(nb, -1, np.int64)
-        wud = np.zeros((nb, 2), np.float32)
-        ok = n_fft == 1024 and n_mels <= 128
-        for k in range(nb):
-            nz = np.nonzero(melb[:, k])[0]
-            if len(nz) == 0 or not ok:
-                continue
-            if len(nz) > 2 or (len(nz) == 2 and nz[1] != nz[0] + 1):
-                ok = False
-            elif len(nz) == 2:
-                seg[k], wud[k, 0], wud[k, 1] = nz[1], melb[nz[1], k], melb[nz[0], k]
-            elif k <= peak[nz[0]]:                     # one filter only, on its rising side (or at its peak)
-                seg[k], wud[k, 0] = nz[0], melb[nz[0], k]
-            else:                                      # ... on its falling side: the segment above
-                seg[k], wud[k, 1] = nz[0] + 1, melb[nz[0], k]
-        seg_lo, seg_len = np.zeros(n_mels + 1, np.int32), np.zeros(n_mels + 1, np.int32)
-        if ok:
-            for m in range(n_mels + 1):
-                ks = np.nonzero(seg == m)[0]
-                if len(ks) == 0:
-                    continue
-                if ks[-1] - ks[0] + 1 != len(ks):
-                    ok = False
-                    break
-                seg_lo[m], seg_len[m] = ks[0], len(ks)
-        if ok:      # the identity the kernel relies on, checked on the tables themselves
-            rec = np.zeros_like(melb)
-            for m in range(n_mels):
-                sl = slice(seg_lo[m], seg_lo[m] + seg_len[m])
-                rec[m, sl] += wud[sl, 0]
-                sl = slice(seg_lo[m + 1], seg_lo[m + 1] + seg_len[m + 1])
-                rec[m, sl] += wud[sl, 1]
-            ok = bool(np.array_equal(rec, melb))
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        _FFT8_TABLES[key] = (t(seg_lo), t(seg_len), t(wud)) if ok else None
+        seg = segment_tables(mel_basis(sr, n_fft, n_mels, fmin, fmax).T) if n_fft == 1024 and n_mels <= 128 else None
+        _FFT8_TABLES[key] = None if seg is None else tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in seg[:3])
     return _FFT8_TABLES[key]
 
 

@@ -69,6 +69,11 @@ def _need_cuda(*ts):
             raise RuntimeError("seq2seq_vc_amd kernels need GPU tensors (there is no CPU path)")
 
 
+def _f32c(t, shape, name):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: contiguous fp32 {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}")
+
+
 # ----------------------------------------------------------------------------------------------
 # dropout seed state: kernels read (*seed_base + seed_off); the base lives in device memory so a
 # captured hipGraph draws fresh masks on every replay once the trainer bumps it.

@@ -1,25 +1,14 @@
 """Launchers of the Griffin-Lim kernels (csrc/griffin_lim.hip; C ABI in include/s2svc_hip.h).  Non-differentiable, GPU tensors only,
 fp32; every argument after the host-side table build is device-resident, so a sequence of these launches is capturable."""
-import numpy as np
 import torch
 
 from .. import _lib
-from .kernels import _need_cuda, ptr, stream
+from .fft_tables import hann_padded, pad_vec4, packed_table  # noqa: F401  (hann_padded: imported from here by tests and tools)
+from .kernels import _f32c, _need_cuda, ptr, stream
 
 N_FFT = (512, 1024, 2048)
 _TABLES = {}
 LAUNCHES = 0                 # launches queued by this module since import (tests and the bench read the difference around a call)
-
-
-def hann_padded(n_fft, win_length=None):
-    """Periodic Hann window of win_length points, centred and zero-padded to n_fft -> float64 (librosa's get_window + pad_center)."""
-    wl = n_fft if win_length is None else int(win_length)
-    if not 0 < wl <= n_fft:
-        raise ValueError(f"win_length must be in 1 .. n_fft, got {wl}")
-    win = np.zeros(n_fft)
-    lp = (n_fft - wl) // 2
-    win[lp:lp + wl] = 0.5 - 0.5 * np.cos(2 * np.pi * np.arange(wl) / wl)
-    return win
 
 
 def tables(device, n_fft, win_length=None):
@@ -28,20 +17,8 @@ def tables(device, n_fft, win_length=None):
         raise ValueError(f"n_fft must be one of {N_FFT}, got {n_fft}")
     key = (str(device), n_fft, win_length)
     if key not in _TABLES:
-        h = n_fft // 2
-        a = -2 * np.pi * np.arange(h) / h
-        w_half = np.stack([np.cos(a), np.sin(a)], 1)
-        a = -2 * np.pi * np.arange(h + 1) / n_fft
-        w_full = np.stack([np.cos(a), np.sin(a)], 1)
-        packed = np.concatenate([w_half.reshape(-1), w_full.reshape(-1), hann_padded(n_fft, win_length)]).astype(np.float32)
-        packed = np.concatenate([packed, np.zeros((-len(packed)) % 4, np.float32)])
-        _TABLES[key] = torch.from_numpy(packed).to(device)
+        _TABLES[key] = torch.from_numpy(pad_vec4(packed_table(n_fft, win_length))).to(device)
     return _TABLES[key]
-
-
-def _f32c(t, shape, name):
-    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: contiguous fp32 {tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}")
 
 
 def _lens(lens, B):

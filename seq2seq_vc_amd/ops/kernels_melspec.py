@@ -5,8 +5,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .kernels import _need_cuda, ptr, stream
-from .kernels_griffin_lim import _f32c
+from .fft_tables import dense_from_segments, segment_tables  # noqa: F401  (imported from here by the module, tests and tools)
+from .kernels import _f32c, _need_cuda, ptr, stream
 from .kernels_griffin_lim import tables as fft_tables
 
 N_FFT = 1024
@@ -41,54 +41,6 @@ def mel_filterbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=None):
         lo, ce, hi = pts[i], pts[i + 1], pts[i + 2]
         fb[:, i] = np.clip(np.minimum((freqs - lo) / (ce - lo), (hi - freqs) / (hi - ce)), 0, None) * (2.0 / (hi - lo))
     return fb
-
-
-def segment_tables(fb):
-    """Segment form of a (bins, n_mels) mel basis, or None if it does not have the structure the kernels need: every bin has at most
-    two non-zero weights, in neighbouring filters.  Segment s (0 .. n_mels) = the bins between the peaks of filters s - 1 and s: rising
-    side of filter s (weight wud[k][0]), falling side of filter s - 1 (wud[k][1]), so that
-        mel[m] = sum over segment m of wud[:, 0] |X| + sum over segment m + 1 of wud[:, 1] |X|.
-    -> (seg_lo, seg_len (n_mels + 1) int32, wud (bins, 2) in fb's dtype, bin_seg (bins) int32: the segment of every bin, 0 with zero
-    weights where no filter reaches)."""
-    fb = np.asarray(fb)
-    nb, n_mels = fb.shape
-    peak = fb.argmax(axis=0)
-    seg = np.full(nb, -1, np.int64)
-    wud = np.zeros((nb, 2), fb.dtype)
-    for k in range(nb):
-        nz = np.nonzero(fb[k])[0]
-        if len(nz) == 0:
-            continue
-        if len(nz) > 2 or (len(nz) == 2 and nz[1] != nz[0] + 1):
-            return None
-        if len(nz) == 2:
-            seg[k], wud[k, 0], wud[k, 1] = nz[1], fb[k, nz[1]], fb[k, nz[0]]
-        elif k <= peak[nz[0]]:                         # one filter only, on its rising side (or at its peak)
-            seg[k], wud[k, 0] = nz[0], fb[k, nz[0]]
-        else:                                          # ... on its falling side: the segment above
-            seg[k], wud[k, 1] = nz[0] + 1, fb[k, nz[0]]
-    seg_lo, seg_len = np.zeros(n_mels + 1, np.int32), np.zeros(n_mels + 1, np.int32)
-    for m in range(n_mels + 1):
-        ks = np.nonzero(seg == m)[0]
-        if len(ks) == 0:
-            continue
-        if ks[-1] - ks[0] + 1 != len(ks):
-            return None
-        seg_lo[m], seg_len[m] = ks[0], len(ks)
-    if not np.array_equal(dense_from_segments(seg_lo, seg_len, wud, n_mels), fb):      # the identity the kernels rely on
-        return None
-    return seg_lo, seg_len, wud, np.maximum(seg, 0).astype(np.int32)
-
-
-def dense_from_segments(seg_lo, seg_len, wud, n_mels):
-    """The (bins, n_mels) basis the segment tables stand for."""
-    rec = np.zeros((wud.shape[0], n_mels), wud.dtype)
-    for m in range(n_mels):
-        sl = slice(seg_lo[m], seg_lo[m] + seg_len[m])
-        rec[sl, m] += wud[sl, 0]
-        sl = slice(seg_lo[m + 1], seg_lo[m + 1] + seg_len[m + 1])
-        rec[sl, m] += wud[sl, 1]
-    return rec
 
 
 def melspec_supported(n_fft, win_length, n_mels):
