@@ -462,7 +462,7 @@ int s2svc_convmod_infer(int dtype, int B, int Tn, int C, int ks, const void* y2,
                         const float* run_var, const float* gamma, const float* beta, float eps, void* out, const int32_t* vlens,
                         void* stream);
 
-/* BatchNorm1d (training mode) + activation + dropout on channel-last bf16 rows, C % 8 == 0, 16-byte accesses (csrc/convmod.hip).
+/* BatchNorm1d (training mode) + activation + dropout on channel-last bf16 rows, C % 8 == 0, 16-byte accesses (csrc/batchnorm.hip).
    replaces: modules/pre_postnets.py:108-165 (BatchNorm1d -> Tanh -> Dropout of the Postnet layers) and its autograd backward.
      s2svc_bn_stats_vec: mean / rstd over (rows, C) + torch's running statistics; ws >= ceil(rows / 64) * 2 * C floats.
      s2svc_bn_act_apply_vec: y = dropout(act((x - mean) * rstd * gamma + beta)); pre_act (or NULL) = the value before act.

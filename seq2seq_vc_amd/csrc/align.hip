@@ -217,11 +217,6 @@ __global__ __launch_bounds__(256) void gauss_probs_kernel(int B, int Tf, int Tx,
   }
 }
 
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int s2svc_pairwise_l2_logsoftmax(int dtype, int B, int Tf, int Tx, int A, const void* feats, const void* text,

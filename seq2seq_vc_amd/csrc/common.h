@@ -123,6 +123,19 @@ __device__ __forceinline__ float act_apply(float x, int act) {
     default: return x;
   }
 }
+// act'(.) for y = dropout(act(x)) from what the forward pass saved: s = the OUTPUT y for relu / tanh / sigmoid (their derivatives
+// are functions of the output; m = the element's keep-scale, 0 when dropped), the pre-activation x for swish / gelu
+__device__ __forceinline__ float act_grad_from_saved(float s, float m, int act) {
+  if (act == S2S_ACT_RELU) return s > 0.f ? 1.f : 0.f;
+  if (act == S2S_ACT_TANH) { const float yv = m > 0.f ? s / m : 0.f; return 1.f - yv * yv; }
+  if (act == S2S_ACT_SIGMOID) { const float yv = m > 0.f ? s / m : 0.f; return yv * (1.f - yv); }
+  if (act == S2S_ACT_SWISH) { const float sg = 1.f / (1.f + expf(-s)); return sg * (1.f + s * (1.f - sg)); }
+  if (act == S2S_ACT_GELU) {
+    const float cdf = 0.5f * (1.f + erff(s * 0.70710678118654752f));
+    return cdf + s * 0.3989422804014327f * expf(-0.5f * s * s);
+  }
+  return 1.f;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Counter-based RNG for dropout masks: a mask is a pure function of (seed, element index), so backward kernels
@@ -163,6 +176,16 @@ __device__ __forceinline__ void load_f32x8(const float* p, float (&f)[8]) {
   const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
   f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
+__device__ __forceinline__ void st8(float* p, const float (&f)[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
+}
+__device__ __forceinline__ void st8(bf16_t* p, const float (&f)[8]) { *reinterpret_cast<uint4*>(p) = pack_bf16x8(f); }
+// per-channel parameters (fp32 slices of a flat parameter buffer: 4-byte alignment is all that is guaranteed)
+__device__ __forceinline__ void ldp8(const float* __restrict__ p, float (&f)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = p[e];
+}
 // keep-scales of 8 consecutive elements starting at idx (idx % 8 == 0): two draws, the fields dropout_scale() reads
 __device__ __forceinline__ void dropout_scale8(uint64_t seed, uint64_t idx, float p, float inv_keep, float (&m)[8]) {
   const uint32_t thr = dropout_threshold(p);
@@ -192,6 +215,13 @@ __device__ __forceinline__ int rows_present(int rows, int Tn, const int32_t* __r
   for (int b = 0; b < rows / Tn; ++b) n += vlens[b] < Tn ? (vlens[b] > 0 ? vlens[b] : 0) : Tn;
   return n;
 }
+
+// grid of a grid-stride element-wise kernel: 256-thread blocks, capped at 2048 blocks (8 per CU)
+inline int ew_blocks(int64_t total) {
+  int64_t b = (total + 255) / 256;
+  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
+}
+inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // error plumbing shared by all translation units (defined in api.hip)
 extern "C" void s2svc_set_error(const char* msg);

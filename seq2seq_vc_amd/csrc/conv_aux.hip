@@ -149,11 +149,6 @@ __global__ void interp_nearest_rows_kernel(int B, int Tin_cap, int Tout_cap, int
   }
 }
 
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int s2svc_col2im_s2(int dtype, int B, int T1, int F1, int C, int T2, int F2, const void* dcols, void* dx,

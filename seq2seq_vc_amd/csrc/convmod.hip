@@ -11,8 +11,9 @@
 // A workgroup owns 64 frames x 64 channels of one utterance (+ (k-1)/2 halo frames each side, zero outside the utterance as the
 // convolution's 'same' padding; padded frames inside T are data, exactly like the reference).  HBM-bound: every tensor is read
 // once per tile (+ 22 % halo at k = 15) in 16-byte accesses, the taps run on an LDS image [frame][channel] that a lane reads
-// down its own column (conflict-free).  All sums have a fixed order (deterministic).
-#include "common.h"
+// down its own column (conflict-free).  All sums have a fixed order (deterministic): the statistics are the two-stage column sums
+// of colsum.h, their second stages ([+ finalize], [+ sum]) the kernels of batchnorm.hip.
+#include "colsum.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
@@ -21,17 +22,6 @@ constexpr int TT = 64, CT = 64, FR = TT / 4;
 
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 __device__ __forceinline__ float round_bf(float v) { return bf2f(f2bf(v)); }
-
-// per-channel parameters (fp32 slices of a flat parameter buffer: 4-byte alignment is all that is guaranteed)
-__device__ __forceinline__ void ldp8(const float* __restrict__ p, float (&f)[8]) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = p[e];
-}
-
-__device__ __forceinline__ void st8(float* p, const float (&f)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-}
 
 template <int KS>
 __global__ __launch_bounds__(256) void convmod_fwd_kernel(int Tn, int C, const bf16_t* __restrict__ y2, const float* __restrict__ w,
@@ -91,14 +81,7 @@ __global__ __launch_bounds__(256) void convmod_fwd_kernel(int Tn, int C, const b
   __syncthreads();
 #pragma unroll
   for (int o = 0; o < FR; ++o) G[(rq * FR + o) * CT + cl] = out[o];
-  red[0][rq][cl] = s0;
-  red[1][rq][cl] = s1;
-  __syncthreads();
-  if (rq == 0) {
-    const int chunk = blockIdx.y;
-    ws[((int64_t)chunk * 2 + 0) * C + c0 + cl] = ((red[0][0][cl] + red[0][1][cl]) + red[0][2][cl]) + red[0][3][cl];
-    ws[((int64_t)chunk * 2 + 1) * C + c0 + cl] = ((red[1][0][cl] + red[1][1][cl]) + red[1][2][cl]) + red[1][3][cl];
-  }
+  colsum_store_pair(s0, s1, red, rq, cl, blockIdx.y, C, c0 + cl, ws);      // (its barrier also covers the z tile in G)
   // ---- phase 3: the z tile, 16 bytes per lane
 #pragma unroll
   for (int i = 0; i < TT / 32; ++i) {
@@ -108,43 +91,6 @@ __global__ __launch_bounds__(256) void convmod_fwd_kernel(int Tn, int C, const b
       load_f32x8(&G[r * CT + v * 8], f);
       *reinterpret_cast<uint4*>(z + ((int64_t)b * Tn + t) * C + c0 + v * 8) = pack_bf16x8(f);
     }
-  }
-}
-
-// sum of the chunk partials (sum z, sum z^2) -> mean, rstd, running statistics (the arithmetic of bn_stage2_finalize_kernel)
-__global__ __launch_bounds__(256) void convmod_bn_finalize_kernel(int C, int chunks, const float* __restrict__ ws, int rows, float eps,
-                                                                  float momentum, float* __restrict__ mean, float* __restrict__ rstd,
-                                                                  float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                                  int64_t* __restrict__ num_batches, int Tn,
-                                                                  const int32_t* __restrict__ vlens) {
-  const int n = rows_present(rows, Tn, vlens);
-  __shared__ float sh[2][4][64];
-  const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  float t0 = 0.f, t1 = 0.f;
-  if (c < C) {
-#pragma unroll 8
-    for (int k = kg; k < chunks; k += 4) {        // same order of additions, 16 loads in flight
-      t0 += ws[((int64_t)k * 2 + 0) * C + c];
-      t1 += ws[((int64_t)k * 2 + 1) * C + c];
-    }
-  }
-  sh[0][kg][cl] = t0;
-  sh[1][kg][cl] = t1;
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) *num_batches += 1;
-  if (kg != 0 || c >= C) return;
-  const float scale = 1.0f / (float)n;
-  const float m = (((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl]) * scale;
-  const float ex2 = (((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl]) * scale;
-  float vc = ex2 - m * m;
-  vc = vc > 0.f ? vc : 0.f;
-  mean[c] = m;
-  rstd[c] = 1.0f / sqrtf(vc + eps);
-  if (run_mean) {
-    run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * m;
-    const float unb = n > 1 ? vc * ((float)n / (float)(n - 1)) : vc;
-    run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
   }
 }
 
@@ -193,7 +139,7 @@ __global__ __launch_bounds__(256) void convmod_bwd_stats_kernel(int rows, int C,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 float* __restrict__ ws, int Tn, const int32_t* __restrict__ vlens) {
   __shared__ float sh[2][4][CT];
-  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3;
   const int c = blockIdx.x * CT + v * 8;
   const int r0 = blockIdx.y * 64;
   uint4 dv[2], zv[2];
@@ -228,49 +174,7 @@ __global__ __launch_bounds__(256) void convmod_bwd_stats_kernel(int rows, int C,
       a1[e] += d * xh;
     }
   }
-  // lanes with the same vector lane v hold the wave's 8 rows: butterfly over lane bits 3..5
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    a0[e] = xor32_sum(xor16_sum(xor8_sum(a0[e])));      // (DPP / permlane swaps instead of ds_bpermute, common.h)
-    a1[e] = xor32_sum(xor16_sum(xor8_sum(a1[e])));
-  }
-  if (lane < 8) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sh[0][wave][v * 8 + e] = a0[e]; sh[1][wave][v * 8 + e] = a1[e]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < CT) {
-    const int cl = threadIdx.x;
-    ws[((int64_t)blockIdx.y * 2 + 0) * C + blockIdx.x * CT + cl] = ((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl];
-    ws[((int64_t)blockIdx.y * 2 + 1) * C + blockIdx.x * CT + cl] = ((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl];
-  }
-}
-
-// sum of the chunk partials -> sdy, sdyx; optionally accumulated into the gradient slots of beta / gamma
-__global__ __launch_bounds__(256) void convmod_sum2_kernel(int C, int chunks, const float* __restrict__ ws, float* __restrict__ sdy,
-                                                           float* __restrict__ sdyx, float* __restrict__ dbeta_acc,
-                                                           float* __restrict__ dgamma_acc) {
-  __shared__ float sh[2][4][64];
-  const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  float t0 = 0.f, t1 = 0.f;
-  if (c < C) {
-#pragma unroll 8
-    for (int k = kg; k < chunks; k += 4) {        // same order of additions, 16 loads in flight
-      t0 += ws[((int64_t)k * 2 + 0) * C + c];
-      t1 += ws[((int64_t)k * 2 + 1) * C + c];
-    }
-  }
-  sh[0][kg][cl] = t0;
-  sh[1][kg][cl] = t1;
-  __syncthreads();
-  if (kg != 0 || c >= C) return;
-  t0 = ((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl];
-  t1 = ((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl];
-  sdy[c] = t0;
-  sdyx[c] = t1;
-  if (dbeta_acc) dbeta_acc[c] += t0;
-  if (dgamma_acc) dgamma_acc[c] += t1;
+  colsum_reduce8(a0, a1, sh, blockIdx.y, C, blockIdx.x * CT, ws);
 }
 
 template <int KS>
@@ -413,217 +317,13 @@ __global__ void convmod_wgrad_final_kernel(int C, int ks, int chunks, const floa
   const int n = C * (ks + 1);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float t = 0.f;
-#pragma unroll 16
-  for (int k = 0; k < chunks; ++k) t += wsw[(int64_t)k * n + i];      // same order of additions, 16 loads in flight
+  const float t = colsum_partials(wsw, chunks, n, i);
   const int c = i / (ks + 1), j = i - c * (ks + 1);
   if (j < ks) {
     if (dw) dw[c * ks + j] = (accumulate ? dw[c * ks + j] : 0.f) + t;
   } else if (db) {
     db[c] = (accumulate ? db[c] : 0.f) + t;
   }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// BatchNorm1d (training) + activation + dropout on channel-last rows, bf16, C % 8 == 0, in 16-byte accesses -- the Postnet layers
-// (pre_postnets.py:108-165: Conv1d -> BatchNorm1d -> Tanh -> Dropout).  Same launch count forward as the scalar kernels of norm.hip
-// (statistics, finalize, apply) but vector loads; backward 3 launches instead of 4 + 2: the activation / dropout derivative is
-// recomputed inside the statistics pass and inside the data-gradient pass instead of being written by a kernel of its own, and the
-// BatchNorm parameter gradients are added to their slots by the reduction's second stage.
-// A workgroup = 64 channels (8 vector lanes) x 64 rows; sums in a fixed order.
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float act_grad_saved(float s, float m, int act) {      // elementwise.hip: act_grad_from_saved
-  if (act == S2S_ACT_RELU) return s > 0.f ? 1.f : 0.f;
-  if (act == S2S_ACT_TANH) { const float yv = m > 0.f ? s / m : 0.f; return 1.f - yv * yv; }
-  if (act == S2S_ACT_SIGMOID) { const float yv = m > 0.f ? s / m : 0.f; return yv * (1.f - yv); }
-  if (act == S2S_ACT_SWISH) { const float sg = 1.f / (1.f + expf(-s)); return sg * (1.f + s * (1.f - sg)); }
-  if (act == S2S_ACT_GELU) {
-    const float cdf = 0.5f * (1.f + erff(s * 0.70710678118654752f));
-    return cdf + s * 0.3989422804014327f * expf(-0.5f * s * s);
-  }
-  return 1.f;
-}
-
-// reduce a0 / a1 (8 channels per lane, 8 rows per wave) over the workgroup's rows -> ws[chunk][2][C]
-__device__ __forceinline__ void bn_chunk_reduce(float (&a0)[8], float (&a1)[8], float (&sh)[2][4][CT], int C, int c, float* __restrict__ ws) {
-  const int v = threadIdx.x & 7, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    a0[e] = xor32_sum(xor16_sum(xor8_sum(a0[e])));      // (DPP / permlane swaps instead of ds_bpermute, common.h)
-    a1[e] = xor32_sum(xor16_sum(xor8_sum(a1[e])));
-  }
-  if (lane < 8) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { sh[0][wave][v * 8 + e] = a0[e]; sh[1][wave][v * 8 + e] = a1[e]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < CT) {
-    const int cl = threadIdx.x, cc = blockIdx.x * CT + cl;
-    if (cc < C) {
-      ws[((int64_t)blockIdx.y * 2 + 0) * C + cc] = ((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl];
-      ws[((int64_t)blockIdx.y * 2 + 1) * C + cc] = ((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl];
-    }
-  }
-  (void)c;
-}
-
-__global__ __launch_bounds__(256) void bn_stats_vec_kernel(int rows, int C, const bf16_t* __restrict__ x, float* __restrict__ ws, int rpc,
-                                                           int Tn, const int32_t* __restrict__ vlens) {
-  __shared__ float sh[2][4][CT];
-  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3;
-  const int c = blockIdx.x * CT + v * 8;
-  const int r0 = blockIdx.y * rpc;
-  const int r1 = r0 + rpc < rows ? r0 + rpc : rows;
-  float a0[8], a1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
-  if (c < C) {
-#pragma unroll 4
-    for (int r = r0 + r8; r < r1; r += 32) {
-      if (!row_present(r, Tn, vlens)) continue;
-      float f[8];
-      unpack_bf16x8(*reinterpret_cast<const uint4*>(x + (int64_t)r * C + c), f);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { a0[e] += f[e]; a1[e] += f[e] * f[e]; }
-    }
-  }
-  bn_chunk_reduce(a0, a1, sh, C, c, ws);
-}
-
-// y = dropout(act((x - mean) * rstd * gamma + beta)); pre_act (optional) = the BatchNorm output before the activation
-__global__ __launch_bounds__(256) void bn_act_apply_vec_kernel(int rows, int C, const bf16_t* __restrict__ x, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                                               const float* __restrict__ beta, int act, float p,
-                                                               const uint64_t* seed_base, uint64_t seed_off, bf16_t* __restrict__ y,
-                                                               bf16_t* __restrict__ pre_act, int rows_per_wg, int Tn,
-                                                               const int32_t* __restrict__ vlens) {
-  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3;
-  const int c = blockIdx.x * CT + v * 8;
-  if (c >= C) return;
-  const int r0 = blockIdx.y * rows_per_wg;
-  const int r1 = r0 + rows_per_wg < rows ? r0 + rows_per_wg : rows;
-  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
-  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  float m[8], rs[8], ga[8], be[8];
-  ldp8(mean + c, m);
-  ldp8(rstd + c, rs);
-  ldp8(gamma + c, ga);
-  ldp8(beta + c, be);
-#pragma unroll 2
-  for (int r = r0 + r8; r < r1; r += 32) {
-    const int64_t o = (int64_t)r * C + c;
-    float f[8], mk[8];
-    if (!row_present(r, Tn, vlens)) {               // absent frame: the next convolution's zero padding
-      if (pre_act) *reinterpret_cast<uint4*>(pre_act + o) = make_uint4(0, 0, 0, 0);
-      *reinterpret_cast<uint4*>(y + o) = make_uint4(0, 0, 0, 0);
-      continue;
-    }
-    unpack_bf16x8(*reinterpret_cast<const uint4*>(x + o), f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (f[e] - m[e]) * rs[e] * ga[e] + be[e];
-    if (pre_act) *reinterpret_cast<uint4*>(pre_act + o) = pack_bf16x8(f);
-    if (p > 0.f) dropout_scale8(seed, (uint64_t)o, p, inv_keep, mk);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      f[e] = act_apply(f[e], act);
-      if (p > 0.f) f[e] *= mk[e];
-    }
-    *reinterpret_cast<uint4*>(y + o) = pack_bf16x8(f);
-  }
-}
-
-// g = dz * mask * act'(saved);  per-chunk sums of g and g * xhat
-__global__ __launch_bounds__(256) void bn_act_bwd_stats_kernel(int rows, int C, const bf16_t* __restrict__ dz, const bf16_t* __restrict__ saved,
-                                                               const bf16_t* __restrict__ x, const float* __restrict__ mean,
-                                                               const float* __restrict__ rstd, int act, float p,
-                                                               const uint64_t* seed_base, uint64_t seed_off, float* __restrict__ ws, int rpc,
-                                                               int Tn, const int32_t* __restrict__ vlens) {
-  __shared__ float sh[2][4][CT];
-  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3;
-  const int c = blockIdx.x * CT + v * 8;
-  const int r0 = blockIdx.y * rpc;
-  const int r1 = r0 + rpc < rows ? r0 + rpc : rows;
-  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
-  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  float a0[8], a1[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) a0[e] = a1[e] = 0.f;
-  if (c < C) {
-    float m[8], rs[8];
-    ldp8(mean + c, m);
-    ldp8(rstd + c, rs);
-#pragma unroll 2
-    for (int r = r0 + r8; r < r1; r += 32) {
-      if (!row_present(r, Tn, vlens)) continue;
-      const int64_t o = (int64_t)r * C + c;
-      float g[8], sd[8], xx[8], mk[8];
-      unpack_bf16x8(*reinterpret_cast<const uint4*>(dz + o), g);
-      if (saved) unpack_bf16x8(*reinterpret_cast<const uint4*>(saved + o), sd);
-      unpack_bf16x8(*reinterpret_cast<const uint4*>(x + o), xx);
-      if (p > 0.f) dropout_scale8(seed, (uint64_t)o, p, inv_keep, mk);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float mm = p > 0.f ? mk[e] : 1.f;
-        const float gg = g[e] * mm * (saved ? act_grad_saved(sd[e], mm, act) : 1.f);
-        a0[e] += gg;
-        a1[e] += gg * (xx[e] - m[e]) * rs[e];
-      }
-    }
-  }
-  bn_chunk_reduce(a0, a1, sh, C, c, ws);
-}
-
-// dx = gamma * rstd * (g - sum_g / N - xhat * sum_g_xhat / N), g recomputed as above
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(int rows, int C, const bf16_t* __restrict__ dz,
-                                                               const bf16_t* __restrict__ saved, const bf16_t* __restrict__ x,
-                                                               const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                               const float* __restrict__ gamma, const float* __restrict__ sdy,
-                                                               const float* __restrict__ sdyx, int act, float p,
-                                                               const uint64_t* seed_base, uint64_t seed_off, bf16_t* __restrict__ dx,
-                                                               int rows_per_wg, int Tn, const int32_t* __restrict__ vlens) {
-  const int v = threadIdx.x & 7, r8 = threadIdx.x >> 3;
-  const int c = blockIdx.x * CT + v * 8;
-  if (c >= C) return;
-  const float inv_n = 1.0f / (float)rows_present(rows, Tn, vlens);
-  const int r0 = blockIdx.y * rows_per_wg;
-  const int r1 = r0 + rows_per_wg < rows ? r0 + rows_per_wg : rows;
-  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
-  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  float m[8], rs[8], k1[8], k2[8], k3[8];
-  ldp8(mean + c, m);
-  ldp8(rstd + c, rs);
-  ldp8(gamma + c, k1);
-  ldp8(sdy + c, k2);
-  ldp8(sdyx + c, k3);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { k1[e] *= rs[e]; k2[e] *= inv_n; k3[e] *= inv_n; }
-#pragma unroll 2
-  for (int r = r0 + r8; r < r1; r += 32) {
-    const int64_t o = (int64_t)r * C + c;
-    float g[8], sd[8], xx[8], mk[8];
-    if (!row_present(r, Tn, vlens)) {               // absent frame: no gradient leaves it
-      *reinterpret_cast<uint4*>(dx + o) = make_uint4(0, 0, 0, 0);
-      continue;
-    }
-    unpack_bf16x8(*reinterpret_cast<const uint4*>(dz + o), g);
-    if (saved) unpack_bf16x8(*reinterpret_cast<const uint4*>(saved + o), sd);
-    unpack_bf16x8(*reinterpret_cast<const uint4*>(x + o), xx);
-    if (p > 0.f) dropout_scale8(seed, (uint64_t)o, p, inv_keep, mk);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float mm = p > 0.f ? mk[e] : 1.f;
-      const float gg = g[e] * mm * (saved ? act_grad_saved(sd[e], mm, act) : 1.f);
-      g[e] = k1[e] * (gg - k2[e] - (xx[e] - m[e]) * rs[e] * k3[e]);
-    }
-    *reinterpret_cast<uint4*>(dx + o) = pack_bf16x8(g);
-  }
-}
-
-bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-// rows per statistics chunk: 64 for short inputs, more (a multiple of 32) so that there are at most 64 chunk partials to sum
-int bn_rows_per_chunk(int rows) {
-  int rpc = ((rows + 63) / 64 + 31) / 32 * 32;
-  return rpc < 64 ? 64 : rpc;
 }
 
 }  // namespace
@@ -645,10 +345,7 @@ extern "C" int s2svc_convmod_fwd(int B, int Tn, int C, int ks, const void* y2, c
   else S2S_CM_FWD(31);
 #undef S2S_CM_FWD
   S2S_CHECK_LAUNCH("convmod_fwd_kernel");
-  hipLaunchKernelGGL(convmod_bn_finalize_kernel, dim3(C / 64), dim3(256), 0, st, C, B * tchunks, ws, B * Tn, eps, momentum, mean, rstd,
-                     run_mean, run_var, num_batches, Tn, vlens);
-  S2S_CHECK_LAUNCH("convmod_bn_finalize_kernel");
-  return 0;
+  return s2s_bn_stage2_finalize(C, B * tchunks, ws, B * Tn, eps, momentum, mean, rstd, run_mean, run_var, num_batches, Tn, vlens, st);
 }
 
 extern "C" int s2svc_bn_swish_apply(int64_t rows, int C, const void* z, const float* mean, const float* rstd, const float* gamma,
@@ -676,8 +373,7 @@ extern "C" int s2svc_convmod_bwd(int B, int Tn, int C, int ks, const void* da, c
   hipLaunchKernelGGL(convmod_bwd_stats_kernel, dim3(C / CT, chunks), dim3(256), 0, st, rows, C, (const bf16_t*)da, (const bf16_t*)z, mean,
                      rstd, gamma, beta, ws_stats, Tn, vlens);
   S2S_CHECK_LAUNCH("convmod_bwd_stats_kernel");
-  hipLaunchKernelGGL(convmod_sum2_kernel, dim3(C / 64), dim3(256), 0, st, C, chunks, ws_stats, sdy, sdyx, dbeta_acc, dgamma_acc);
-  S2S_CHECK_LAUNCH("convmod_sum2_kernel");
+  if (const int rc = s2s_colsum_pair(C, chunks, ws_stats, sdy, sdyx, dbeta_acc, dgamma_acc, st)) return rc;
   const int tchunks = (Tn + TT - 1) / TT;
   dim3 grid(C / CT, B * tchunks);
 #define S2S_CM_BWD(K)                                                                                                              \
@@ -697,60 +393,5 @@ extern "C" int s2svc_convmod_wgrad_final(int C, int ks, int chunks, const float*
   hipLaunchKernelGGL(convmod_wgrad_final_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, C, ks, chunks, ws_w, dw, db,
                      accumulate);
   S2S_CHECK_LAUNCH("convmod_wgrad_final_kernel");
-  return 0;
-}
-
-// ---- BatchNorm1d (training) + activation + dropout, bf16, C % 8 == 0 (see above) ----
-// mean / rstd of x (rows, C) + running statistics: two launches.  ws >= ceil(rows / 64) * 2 * C floats.
-extern "C" int s2svc_bn_stats_vec(int rows, int C, const void* x, float eps, float momentum, float* mean, float* rstd, float* run_mean,
-                                  float* run_var, int64_t* num_batches, float* ws, int Tn, const int32_t* vlens, void* stream) {
-  S2S_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && x && mean && rstd && ws && aligned16(x), "bn_stats_vec: bad args (bf16, C % 8 == 0)");
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0), "bn_stats_vec: vlens needs rows = B * Tn");
-  hipStream_t st = (hipStream_t)stream;
-  const int rpc = bn_rows_per_chunk(rows), chunks = (rows + rpc - 1) / rpc, ct = (C + CT - 1) / CT;
-  hipLaunchKernelGGL(bn_stats_vec_kernel, dim3(ct, chunks), dim3(256), 0, st, rows, C, (const bf16_t*)x, ws, rpc, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_stats_vec_kernel");
-  hipLaunchKernelGGL(convmod_bn_finalize_kernel, dim3(ct), dim3(256), 0, st, C, chunks, ws, rows, eps, momentum, mean, rstd, run_mean,
-                     run_var, num_batches, Tn, vlens);
-  S2S_CHECK_LAUNCH("convmod_bn_finalize_kernel");
-  return 0;
-}
-
-extern "C" int s2svc_bn_act_apply_vec(int rows, int C, const void* x, const float* mean, const float* rstd, const float* gamma,
-                                      const float* beta, int act, float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* y,
-                                      void* pre_act, int Tn, const int32_t* vlens, void* stream) {
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0), "bn_act_apply_vec: vlens needs rows = B * Tn");
-  S2S_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && x && mean && rstd && gamma && beta && y && aligned16(x) && aligned16(y) &&
-              aligned16(pre_act), "bn_act_apply_vec: bad args (bf16, C % 8 == 0)");
-  const int rpw = 128;
-  hipLaunchKernelGGL(bn_act_apply_vec_kernel, dim3((C + CT - 1) / CT, (rows + rpw - 1) / rpw), dim3(256), 0, (hipStream_t)stream, rows, C,
-                     (const bf16_t*)x, mean, rstd, gamma, beta, act, drop_p, seed_base, seed_off, (bf16_t*)y, (bf16_t*)pre_act, rpw, Tn,
-                     vlens);
-  S2S_CHECK_LAUNCH("bn_act_apply_vec_kernel");
-  return 0;
-}
-
-// dz = gradient of y = dropout(act(BN(x))); saved = y (relu / tanh / sigmoid) or the pre-activation (swish / gelu), NULL for act none
-// without dropout.  -> dx, sdy = sum g, sdyx = sum g * xhat (the gradients of beta / gamma, also ADDED to dbeta_acc / dgamma_acc when
-// given).  Three launches.  ws >= ceil(rows / 64) * 2 * C floats.
-extern "C" int s2svc_bn_act_bwd_vec(int rows, int C, const void* dz, const void* saved, const void* x, const float* mean, const float* rstd,
-                                    const float* gamma, int act, float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* dx,
-                                    float* sdy, float* sdyx, float* dgamma_acc, float* dbeta_acc, float* ws, int Tn, const int32_t* vlens,
-                                    void* stream) {
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0), "bn_act_bwd_vec: vlens needs rows = B * Tn");
-  S2S_REQUIRE(rows > 0 && C > 0 && C % 8 == 0 && dz && x && mean && rstd && gamma && dx && sdy && sdyx && ws && aligned16(dz) &&
-              aligned16(saved) && aligned16(x) && aligned16(dx) && (saved || act == S2S_ACT_NONE), "bn_act_bwd_vec: bad args (bf16, C % 8 == 0)");
-  hipStream_t st = (hipStream_t)stream;
-  const int rpc = bn_rows_per_chunk(rows), chunks = (rows + rpc - 1) / rpc, ct = (C + CT - 1) / CT;
-  hipLaunchKernelGGL(bn_act_bwd_stats_kernel, dim3(ct, chunks), dim3(256), 0, st, rows, C, (const bf16_t*)dz, (const bf16_t*)saved,
-                     (const bf16_t*)x, mean, rstd, act, drop_p, seed_base, seed_off, ws, rpc, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_act_bwd_stats_kernel");
-  hipLaunchKernelGGL(convmod_sum2_kernel, dim3(ct), dim3(256), 0, st, C, chunks, ws, sdy, sdyx, dbeta_acc, dgamma_acc);
-  S2S_CHECK_LAUNCH("convmod_sum2_kernel");
-  const int rpw = 128;
-  hipLaunchKernelGGL(bn_act_bwd_apply_kernel, dim3(ct, (rows + rpw - 1) / rpw), dim3(256), 0, st, rows, C,
-                     (const bf16_t*)dz, (const bf16_t*)saved, (const bf16_t*)x, mean, rstd, gamma, sdy, sdyx, act, drop_p, seed_base,
-                     seed_off, (bf16_t*)dx, rpw, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_act_bwd_apply_kernel");
   return 0;
 }

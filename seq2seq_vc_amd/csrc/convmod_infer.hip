@@ -20,11 +20,6 @@ constexpr int TT = 64, CT = 64, FR = TT / 4, KS_MAX = 31;
 
 __device__ __forceinline__ void ld8(const float* p, float (&f)[8]) { load_f32x8(p, f); }
 __device__ __forceinline__ void ld8(const bf16_t* p, float (&f)[8]) { unpack_bf16x8(*reinterpret_cast<const uint4*>(p), f); }
-__device__ __forceinline__ void st8(float* p, const float (&f)[8]) {
-  *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
-  *reinterpret_cast<float4*>(p + 4) = make_float4(f[4], f[5], f[6], f[7]);
-}
-__device__ __forceinline__ void st8(bf16_t* p, const float (&f)[8]) { *reinterpret_cast<uint4*>(p) = pack_bf16x8(f); }
 
 // KS > 0: the kernel size at compile time; KS == 0: any odd ks <= KS_MAX at run time
 template <typename T, int KS>

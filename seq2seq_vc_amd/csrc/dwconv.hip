@@ -3,7 +3,7 @@
 // reference: modules/conformer/convolution.py:42-51,70 (depthwise_conv, k = 7/15/31) and the dilated
 // depth-separable convs of the VITS flows (modules/vits/flow.py:137-146).  HBM-bound: lanes run along the
 // contiguous channel axis (coalesced), the k taps of a (t, c) output re-read neighbouring rows from L1/L2.
-#include "common.h"
+#include "colsum.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
@@ -235,15 +235,8 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_tiled_kernel(int B, int Tn, 
 __global__ void dwconv_wgrad_final_kernel(int n, int chunks, const float* __restrict__ ws, float* __restrict__ dw, int accumulate) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float t = 0.f;
-#pragma unroll 16
-  for (int k = 0; k < chunks; ++k) t += ws[(int64_t)k * n + i];        // same order of additions, 16 loads in flight
+  const float t = colsum_partials(ws, chunks, n, i);
   dw[i] = (accumulate ? dw[i] : 0.f) + t;
-}
-
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
 }  // namespace

@@ -6,10 +6,6 @@
 
 namespace {
 
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
 #define EW_LOOP(i, total) \
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (total); i += (int64_t)gridDim.x * blockDim.x)
 
@@ -59,18 +55,7 @@ __global__ void act_dropout_bwd_kernel(int64_t n, const T* __restrict__ dz, cons
 }
 
 // bf16, n % 8 == 0, 16-byte aligned: 8 consecutive elements per thread and iteration (one 16-byte load per tensor, one
-// 16-byte store, two RNG draws) -- same values as the scalar kernels above
-__device__ __forceinline__ float act_grad_from_saved(float s, float m, int act) {
-  if (act == S2S_ACT_RELU) return s > 0.f ? 1.f : 0.f;
-  if (act == S2S_ACT_TANH) { const float yv = m > 0.f ? s / m : 0.f; return 1.f - yv * yv; }
-  if (act == S2S_ACT_SIGMOID) { const float yv = m > 0.f ? s / m : 0.f; return yv * (1.f - yv); }
-  if (act == S2S_ACT_SWISH) { const float sg = 1.f / (1.f + expf(-s)); return sg * (1.f + s * (1.f - sg)); }
-  if (act == S2S_ACT_GELU) {
-    const float cdf = 0.5f * (1.f + erff(s * 0.70710678118654752f));
-    return cdf + s * 0.3989422804014327f * expf(-0.5f * s * s);
-  }
-  return 1.f;
-}
+// 16-byte store, two RNG draws) -- same values as the scalar kernels above (act_grad_from_saved: common.h)
 __global__ void act_dropout_fwd_vec_kernel(int64_t n8, const bf16_t* __restrict__ x, int act, float p, const uint64_t* seed_base,
                                            uint64_t seed_off, bf16_t* __restrict__ y) {
   const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;

@@ -40,11 +40,6 @@ __global__ void log_clamp_kernel(int64_t n, int D, const float* __restrict__ x, 
   }
 }
 
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
-}
-
 }  // namespace
 
 extern "C" int s2svc_reflect_pad(int64_t n, int pad, const float* x, float* y, void* stream) {

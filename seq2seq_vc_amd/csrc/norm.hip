@@ -1,8 +1,8 @@
-// LayerNorm (fused with residual-add + dropout), BatchNorm1d over (B*T) rows, and the chunked
-// deterministic column reductions they and the bias gradients share.  All HBM-bound: one read of
+// LayerNorm (fused with residual-add + dropout) and the chunked deterministic column reductions that it,
+// BatchNorm (batchnorm.hip) and the bias gradients share (colsum.h).  All HBM-bound: one read of
 // each input, one write of each output, statistics in fp32 registers / wave shuffles.
 #include <cstring>
-#include "common.h"
+#include "colsum.h"
 #include "../../include/s2svc_hip.h"
 
 namespace {
@@ -415,15 +415,7 @@ __device__ __forceinline__ void colreduce_stage1_body(int rows, int D, int mode,
       }
     }
   }
-  sh[0][rl][cl] = s0;
-  sh[1][rl][cl] = s1;
-  __syncthreads();
-  if (rl == 0 && c < D) {
-    float t0 = sh[0][0][cl] + sh[0][1][cl] + sh[0][2][cl] + sh[0][3][cl];
-    float t1 = sh[1][0][cl] + sh[1][1][cl] + sh[1][2][cl] + sh[1][3][cl];
-    ws[((int64_t)chunk * 2 + 0) * D + c] = t0;
-    ws[((int64_t)chunk * 2 + 1) * D + c] = t1;
-  }
+  colsum_store_pair(s0, s1, sh, rl, cl, chunk, D, c, ws);
 }
 
 // 16-byte variant (bf16, D % 8 == 0, 16-byte aligned tensors): a lane owns 8 consecutive columns, a wave covers 512 columns
@@ -482,19 +474,7 @@ __device__ __forceinline__ void colreduce_stage1_vec_body(int rows, int D, int m
       }
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    sh[0][rl][lane * 8 + e] = s0[e];
-    sh[1][rl][lane * 8 + e] = s1[e];
-  }
-  __syncthreads();
-  // 512 columns x 2 sums: thread t combines column t (sum 0) and column t (sum 1) of its half
-  for (int i = threadIdx.x; i < 1024; i += 256) {
-    const int which = i >> 9, col = i & 511;
-    if (bx * 512 + col < D)
-      ws[((int64_t)chunk * 2 + which) * D + bx * 512 + col] =
-          sh[which][0][col] + sh[which][1][col] + sh[which][2][col] + sh[which][3][col];
-  }
+  colsum_store_pair(s0, s1, sh, rl, lane, chunk, D, bx * 512, ws);
 }
 
 // wide rows only: at D = 384 / 512 (VTN) one workgroup per 512 columns leaves too few workgroups (4.00 -> 4.02 ms per step),
@@ -532,27 +512,13 @@ __global__ __launch_bounds__(256) void colreduce_stage1_vec(int rows, int D, int
   colreduce_stage1_vec_body(rows, D, mode, dy, x, mean, rstd, ws, rows_per_chunk, blockIdx.x, blockIdx.y, shv);
 }
 
-// 64 columns x 4 chunk-groups per workgroup: each thread sums every 4th chunk partial (independent loads), the four
-// groups are combined through LDS in a fixed order
+// stage 2 (colsum.h: 64 columns x 4 chunk groups per workgroup), the totals scaled and stored or accumulated
 __device__ __forceinline__ void colreduce_stage2_body(int D, int chunks, const float* __restrict__ ws, float scale,
                                                       float* __restrict__ out_sum, float* __restrict__ out_dot, int accumulate, int bx,
                                                       float (&sh)[2][4][64]) {
-  const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6;
-  const int c = bx * 64 + cl;
-  float t0 = 0.f, t1 = 0.f;
-  if (c < D) {
-#pragma unroll 8
-    for (int k = kg; k < chunks; k += 4) {        // same order of additions, 16 loads in flight
-      t0 += ws[((int64_t)k * 2 + 0) * D + c];
-      t1 += ws[((int64_t)k * 2 + 1) * D + c];
-    }
-  }
-  sh[0][kg][cl] = t0;
-  sh[1][kg][cl] = t1;
-  __syncthreads();
-  if (kg == 0 && c < D) {
-    t0 = ((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl];
-    t1 = ((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl];
+  const int c = bx * 64 + (threadIdx.x & 63);
+  float t0, t1;
+  if (colsum_finish(D, chunks, ws, bx, sh, t0, t1)) {
     if (out_sum) out_sum[c] = (accumulate ? out_sum[c] : 0.f) + t0 * scale;
     if (out_dot) out_dot[c] = (accumulate ? out_dot[c] : 0.f) + t1 * scale;
   }
@@ -602,132 +568,6 @@ __global__ __launch_bounds__(256) void colreduce_grouped_stage2(const cr_args a)
   const s2svc_colreduce_item& it = a.it[blockIdx.y];
   if ((int)blockIdx.x * 64 >= it.D) return;
   colreduce_stage2_body(it.D, a.chunks[blockIdx.y], it.ws, it.scale, it.out_sum, it.out_dot, it.accumulate, blockIdx.x, sh);
-}
-
-// ------------------------------------------------------------------------------------------------
-// BatchNorm1d apply (channel-last rows): y = dropout(act((x-mean[c])*rstd[c]*gamma[c]+beta[c]))
-// reference: modules/pre_postnets.py:108-165 (Conv1d->BatchNorm1d->Tanh->Dropout) and
-// modules/conformer/convolution.py:73-75 (BatchNorm1d -> Swish).  Padded frames are part of the
-// statistics exactly as in the reference (no masking).
-// ------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void bn_apply_kernel(int64_t total, int C, const T* __restrict__ x, const float* __restrict__ mean,
-                                const float* __restrict__ rstd, const float* __restrict__ gamma,
-                                const float* __restrict__ beta, int act, float p, const uint64_t* seed_base, uint64_t seed_off, T* __restrict__ y,
-                                T* __restrict__ pre_act, int Tn, const int32_t* __restrict__ vlens) {
-  const uint64_t seed = (seed_base ? *seed_base : 0ull) + seed_off;
-  const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    if (vlens && !row_present((int)(i / C), Tn, vlens)) {      // absent frame (common.h): the next convolution's zero padding
-      if (pre_act) stf(pre_act + i, 0.f);
-      stf(y + i, 0.f);
-      continue;
-    }
-    float v = (ldf(x + i) - mean[c]) * rstd[c] * gamma[c] + beta[c];
-    if (pre_act) stf(pre_act + i, v);
-    v = act_apply(v, act);
-    if (p > 0.f) v *= dropout_scale(seed, (uint64_t)i, p, inv_keep);
-    stf(y + i, v);
-  }
-}
-
-// dx = gamma*rstd*(dy - sum_dy/N - xhat*sum_dy_xhat/N)   (training-mode BatchNorm backward)
-// eval mode (use_batch_stats = 0): dx = gamma*rstd*dy
-template <typename T>
-__global__ void bn_bwd_kernel(int64_t total, int C, float inv_n, const T* __restrict__ dy, const T* __restrict__ x,
-                              const float* __restrict__ mean, const float* __restrict__ rstd,
-                              const float* __restrict__ gamma, const float* __restrict__ sum_dy,
-                              const float* __restrict__ sum_dy_xhat, int use_batch_stats, T* __restrict__ dx, int Tn,
-                              const int32_t* __restrict__ vlens) {
-  if (vlens) inv_n = 1.0f / (float)rows_present((int)(total / C), Tn, vlens);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    if (vlens && !row_present((int)(i / C), Tn, vlens)) {      // absent frame: no gradient leaves it
-      stf(dx + i, 0.f);
-      continue;
-    }
-    float g = ldf(dy + i);
-    float v;
-    if (use_batch_stats) {
-      float xh = (ldf(x + i) - mean[c]) * rstd[c];
-      v = gamma[c] * rstd[c] * (g - sum_dy[c] * inv_n - xh * sum_dy_xhat[c] * inv_n);
-    } else {
-      v = gamma[c] * rstd[c] * g;
-    }
-    stf(dx + i, v);
-  }
-}
-
-// var (biased) -> rstd, and the running-statistics update of torch.nn.BatchNorm1d (momentum 0.1,
-// unbiased variance in the running buffer).
-__global__ void bn_finalize_kernel(int C, int n, float eps, float momentum, const float* __restrict__ mean,
-                                   const float* __restrict__ var, float* __restrict__ rstd, float* __restrict__ run_mean,
-                                   float* __restrict__ run_var, int64_t* __restrict__ num_batches, int var_is_ex2, int Tn,
-                                   const int32_t* __restrict__ vlens) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  n = rows_present(n, Tn, vlens);
-  if (c == 0 && num_batches) *num_batches += 1;
-  if (c >= C) return;
-  float vc = var[c];
-  if (var_is_ex2) {                   // `var` holds E[x^2] (one-pass statistics): biased variance = E[x^2] - mean^2
-    vc -= mean[c] * mean[c];
-    vc = vc > 0.f ? vc : 0.f;
-  }
-  rstd[c] = 1.0f / sqrtf(vc + eps);
-  if (run_mean) {
-    run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * mean[c];
-    const float unb = n > 1 ? vc * ((float)n / (float)(n - 1)) : vc;
-    run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-  }
-}
-
-// One-pass training statistics, second half: the stage-2 sum of the chunk partials (colreduce mode 6: sum x, sum x^2 -- same
-// order of additions as colreduce_stage2) and bn_finalize_kernel's arithmetic in ONE launch.
-__global__ __launch_bounds__(256) void bn_stage2_finalize_kernel(int C, int chunks, const float* __restrict__ ws, int n, float eps,
-                                                                 float momentum, float* __restrict__ mean, float* __restrict__ rstd,
-                                                                 float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                                 int64_t* __restrict__ num_batches, int Tn,
-                                                                 const int32_t* __restrict__ vlens) {
-  __shared__ float sh[2][4][64];
-  const int cl = threadIdx.x & 63, kg = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  n = rows_present(n, Tn, vlens);
-  float t0 = 0.f, t1 = 0.f;
-  if (c < C) {
-#pragma unroll 8
-    for (int k = kg; k < chunks; k += 4) {        // same order of additions, 16 loads in flight
-      t0 += ws[((int64_t)k * 2 + 0) * C + c];
-      t1 += ws[((int64_t)k * 2 + 1) * C + c];
-    }
-  }
-  sh[0][kg][cl] = t0;
-  sh[1][kg][cl] = t1;
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) *num_batches += 1;
-  if (kg != 0 || c >= C) return;
-  const float scale = 1.0f / (float)n;
-  const float m = (((sh[0][0][cl] + sh[0][1][cl]) + sh[0][2][cl]) + sh[0][3][cl]) * scale;
-  const float ex2 = (((sh[1][0][cl] + sh[1][1][cl]) + sh[1][2][cl]) + sh[1][3][cl]) * scale;
-  float vc = ex2 - m * m;
-  vc = vc > 0.f ? vc : 0.f;
-  mean[c] = m;
-  rstd[c] = 1.0f / sqrtf(vc + eps);
-  if (run_mean) {
-    run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * m;
-    const float unb = n > 1 ? vc * ((float)n / (float)(n - 1)) : vc;
-    run_var[c] = (1.f - momentum) * run_var[c] + momentum * unb;
-  }
-}
-
-__global__ void rstd_from_var_kernel(int C, float eps, const float* __restrict__ var, float* __restrict__ rstd) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) rstd[c] = 1.0f / sqrtf(var[c] + eps);
-}
-
-inline int ew_blocks(int64_t total) {
-  int64_t b = (total + 255) / 256;
-  return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
 }  // namespace
@@ -857,18 +697,15 @@ extern "C" int s2svc_layernorm_bwd_pg(int dtype, int rows, int D, const void* dy
   return 0;
 }
 
-extern "C" int s2svc_colreduce(int dtype, int rows, int D, int mode, const void* dy, const void* x, const float* mean,
-                               const float* rstd, float scale, float* out_sum, float* out_dot, int accumulate,
-                               float* ws, int ws_chunks, int Tn, const int32_t* vlens, void* stream) {
-  S2S_REQUIRE(rows >= 0 && D > 0 && ws && ws_chunks > 0, "colreduce: bad args");
-  S2S_REQUIRE(mode >= 0 && mode <= 6, "colreduce: bad mode");
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0 && mode != 1 && mode != 5), "colreduce: vlens needs rows = B * Tn (modes 0, 2, 3, 4, 6)");
-  S2S_REQUIRE(scale >= 0.f || rows > 0, "colreduce: scale < 0 (mean over the present rows) needs rows");
-  hipStream_t st = (hipStream_t)stream;
+// Stage 1 of one column reduction (colsum.h declares it: s2svc_bn_stats of batchnorm.hip launches it too): at most ws_chunks chunks of
+// >= 64 rows -> ws[*chunks][2][D]; the kernel by mask / dtype, the 16-byte one where allowed and eligible.
+int s2s_colreduce_stage1(int dtype, int rows, int D, int mode, const void* dy, const void* x, const float* mean, const float* rstd,
+                         float* ws, int ws_chunks, int Tn, const int32_t* vlens, bool allow_vec, hipStream_t st, int* chunks_out) {
   int chunks = (rows + 63) / 64;
   if (chunks > ws_chunks) chunks = ws_chunks;
   if (chunks < 1) chunks = 1;
   const int rpc = (rows + chunks - 1) / chunks;
+  *chunks_out = chunks;
   dim3 grid((D + 63) / 64, chunks), block(256);
   if (vlens && dtype == S2S_F32)
     hipLaunchKernelGGL(colreduce_stage1_masked<float>, grid, block, 0, st, rows, D, mode, (const float*)dy, (const float*)x, mean,
@@ -876,7 +713,7 @@ extern "C" int s2svc_colreduce(int dtype, int rows, int D, int mode, const void*
   else if (vlens)
     hipLaunchKernelGGL(colreduce_stage1_masked<bf16_t>, grid, block, 0, st, rows, D, mode, (const bf16_t*)dy, (const bf16_t*)x,
                        mean, rstd, ws, rpc, Tn, vlens);
-  else if (cr_vec_ok_host(dtype, D, dy, x))
+  else if (allow_vec && cr_vec_ok_host(dtype, D, dy, x))
     hipLaunchKernelGGL(colreduce_stage1_vec, dim3((D + 511) / 512, chunks), block, 0, st, rows, D, mode, (const bf16_t*)dy,
                        (const bf16_t*)x, mean, rstd, ws, rpc);
   else if (dtype == S2S_F32)
@@ -886,6 +723,19 @@ extern "C" int s2svc_colreduce(int dtype, int rows, int D, int mode, const void*
     hipLaunchKernelGGL(colreduce_stage1<bf16_t>, grid, block, 0, st, rows, D, mode, (const bf16_t*)dy, (const bf16_t*)x,
                        mean, rstd, ws, rpc);
   S2S_CHECK_LAUNCH("colreduce_stage1");
+  return 0;
+}
+
+extern "C" int s2svc_colreduce(int dtype, int rows, int D, int mode, const void* dy, const void* x, const float* mean,
+                               const float* rstd, float scale, float* out_sum, float* out_dot, int accumulate,
+                               float* ws, int ws_chunks, int Tn, const int32_t* vlens, void* stream) {
+  S2S_REQUIRE(rows >= 0 && D > 0 && ws && ws_chunks > 0, "colreduce: bad args");
+  S2S_REQUIRE(mode >= 0 && mode <= 6, "colreduce: bad mode");
+  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0 && mode != 1 && mode != 5), "colreduce: vlens needs rows = B * Tn (modes 0, 2, 3, 4, 6)");
+  S2S_REQUIRE(scale >= 0.f || rows > 0, "colreduce: scale < 0 (mean over the present rows) needs rows");
+  hipStream_t st = (hipStream_t)stream;
+  int chunks = 0;
+  if (const int rc = s2s_colreduce_stage1(dtype, rows, D, mode, dy, x, mean, rstd, ws, ws_chunks, Tn, vlens, true, st, &chunks)) return rc;
   hipLaunchKernelGGL(colreduce_stage2, dim3((D + 63) / 64), dim3(256), 0, st, D, chunks, ws, scale, out_sum, out_dot,
                      accumulate, rows, Tn, vlens);
   S2S_CHECK_LAUNCH("colreduce_stage2");
@@ -926,89 +776,5 @@ extern "C" int s2svc_colreduce_grouped(const s2svc_colreduce_item* items, int n,
     hipLaunchKernelGGL(colreduce_grouped_stage2, dim3(max_tiles, a.n), dim3(256), 0, st, a);
     S2S_CHECK_LAUNCH("colreduce_grouped_stage2");
   }
-  return 0;
-}
-
-extern "C" int s2svc_bn_finalize(int C, int n, float eps, float momentum, const float* mean, const float* var,
-                                 float* rstd, float* run_mean, float* run_var, int64_t* num_batches, int var_is_ex2, int Tn,
-                                 const int32_t* vlens, void* stream) {
-  S2S_REQUIRE(!vlens || (Tn > 0 && n % Tn == 0), "bn_finalize: vlens needs n = B * Tn");
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, C, n, eps, momentum,
-                     mean, var, rstd, run_mean, run_var, num_batches, var_is_ex2, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_finalize_kernel");
-  return 0;
-}
-
-// mean / rstd of a training-mode BatchNorm1d over (rows, C) in TWO launches (one pass over x: fp32 sums of x and x^2 per chunk,
-// then sum of the partials + variance + rstd + running statistics); ws >= ws_chunks*2*C floats.  Same values as
-// s2svc_colreduce(mode 6, scale 1/rows) + s2svc_bn_finalize(var_is_ex2 = 1), one launch less.
-extern "C" int s2svc_bn_stats(int dtype, int rows, int C, const void* x, float eps, float momentum, float* mean, float* rstd,
-                              float* run_mean, float* run_var, int64_t* num_batches, float* ws, int ws_chunks, int Tn,
-                              const int32_t* vlens, void* stream) {
-  S2S_REQUIRE(rows > 0 && C > 0 && x && mean && rstd && ws && ws_chunks > 0, "bn_stats: bad args");
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0), "bn_stats: vlens needs rows = B * Tn");
-  S2S_REQUIRE(dtype == S2S_F32 || dtype == S2S_BF16, "bn_stats: bad dtype");
-  hipStream_t st = (hipStream_t)stream;
-  int chunks = (rows + 63) / 64;
-  if (chunks > ws_chunks) chunks = ws_chunks;
-  const int rpc = (rows + chunks - 1) / chunks;
-  dim3 grid((C + 63) / 64, chunks), block(256);
-  if (vlens && dtype == S2S_F32)
-    hipLaunchKernelGGL(colreduce_stage1_masked<float>, grid, block, 0, st, rows, C, 6, (const float*)nullptr, (const float*)x,
-                       (const float*)nullptr, (const float*)nullptr, ws, rpc, Tn, vlens);
-  else if (vlens)
-    hipLaunchKernelGGL(colreduce_stage1_masked<bf16_t>, grid, block, 0, st, rows, C, 6, (const bf16_t*)nullptr, (const bf16_t*)x,
-                       (const float*)nullptr, (const float*)nullptr, ws, rpc, Tn, vlens);
-  else if (dtype == S2S_F32)
-    hipLaunchKernelGGL(colreduce_stage1<float>, grid, block, 0, st, rows, C, 6, (const float*)nullptr, (const float*)x,
-                       (const float*)nullptr, (const float*)nullptr, ws, rpc);
-  else
-    hipLaunchKernelGGL(colreduce_stage1<bf16_t>, grid, block, 0, st, rows, C, 6, (const bf16_t*)nullptr, (const bf16_t*)x,
-                       (const float*)nullptr, (const float*)nullptr, ws, rpc);
-  S2S_CHECK_LAUNCH("colreduce_stage1");
-  hipLaunchKernelGGL(bn_stage2_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, st, C, chunks, ws, rows, eps, momentum, mean,
-                     rstd, run_mean, run_var, num_batches, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_stage2_finalize_kernel");
-  return 0;
-}
-
-extern "C" int s2svc_rstd_from_var(int C, float eps, const float* var, float* rstd, void* stream) {
-  hipLaunchKernelGGL(rstd_from_var_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, C, eps, var, rstd);
-  S2S_CHECK_LAUNCH("rstd_from_var_kernel");
-  return 0;
-}
-
-extern "C" int s2svc_bn_apply(int dtype, int64_t rows, int C, const void* x, const float* mean, const float* rstd,
-                              const float* gamma, const float* beta, int act, float drop_p, const uint64_t* seed_base, uint64_t seed_off, void* y,
-                              void* pre_act, int Tn, const int32_t* vlens, void* stream) {
-  const int64_t total = rows * C;
-  if (total == 0) return 0;
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0 && rows < (1ll << 31)), "bn_apply: vlens needs rows = B * Tn");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == S2S_F32)
-    hipLaunchKernelGGL(bn_apply_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, st, total, C, (const float*)x, mean,
-                       rstd, gamma, beta, act, drop_p, seed_base, seed_off, (float*)y, (float*)pre_act, Tn, vlens);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, st, total, C, (const bf16_t*)x, mean,
-                       rstd, gamma, beta, act, drop_p, seed_base, seed_off, (bf16_t*)y, (bf16_t*)pre_act, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_apply_kernel");
-  return 0;
-}
-
-extern "C" int s2svc_bn_bwd(int dtype, int64_t rows, int C, const void* dy, const void* x, const float* mean,
-                            const float* rstd, const float* gamma, const float* sum_dy, const float* sum_dy_xhat,
-                            int use_batch_stats, void* dx, int Tn, const int32_t* vlens, void* stream) {
-  const int64_t total = rows * C;
-  if (total == 0) return 0;
-  S2S_REQUIRE(!vlens || (Tn > 0 && rows % Tn == 0 && rows < (1ll << 31)), "bn_bwd: vlens needs rows = B * Tn");
-  hipStream_t st = (hipStream_t)stream;
-  const float inv_n = 1.0f / (float)rows;
-  if (dtype == S2S_F32)
-    hipLaunchKernelGGL(bn_bwd_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, st, total, C, inv_n, (const float*)dy,
-                       (const float*)x, mean, rstd, gamma, sum_dy, sum_dy_xhat, use_batch_stats, (float*)dx, Tn, vlens);
-  else
-    hipLaunchKernelGGL(bn_bwd_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, st, total, C, inv_n, (const bf16_t*)dy,
-                       (const bf16_t*)x, mean, rstd, gamma, sum_dy, sum_dy_xhat, use_batch_stats, (bf16_t*)dx, Tn, vlens);
-  S2S_CHECK_LAUNCH("bn_bwd_kernel");
   return 0;
 }

@@ -1791,7 +1791,7 @@ class _BatchNormAct(Function):
         Tn = x.shape[-2] if vlens is not None else 0       # absent rows (include/s2svc_hip.h): out of the statistics, zero in y and dx
         ctx.vl = (vlens, Tn)
         ctx.vec = training and K.bn_vec_ok(x)
-        if ctx.vec:     # bf16: 16-byte kernels; the backward pass recomputes the activation / dropout derivative (csrc/convmod.hip)
+        if ctx.vec:     # bf16: 16-byte kernels; the backward pass recomputes the activation / dropout derivative (csrc/batchnorm.hip)
             mean, rstd = K.bn_stats_vec(x, rows, C, eps, momentum, run_mean, run_var, num_batches, vlens=vlens, Tn=Tn)
             need_pre = act in ("swish", "gelu")
             y, pre = K.bn_act_apply_vec(x, mean, rstd, gamma.detach(), beta.detach(), act=act, p=p, seed=seed, want_pre=need_pre,

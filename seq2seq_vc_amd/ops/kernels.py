@@ -782,7 +782,7 @@ def colreduce_partials(ws, chunks, D, out_sum, out_dot):
     _lib.check(_lib.lib().s2svc_colreduce_grouped(ctypes.addressof(arr), 1, stream()), "colreduce_grouped")
 
 
-_WS_CHUNKS = 64
+_WS_CHUNKS = 64                # partial rows per two-stage column sum (csrc/colsum.h); ops/kernels_aas.py imports it
 
 
 def colreduce(mode, dy, x=None, mean=None, rstd=None, scale=1.0, want_dot=False, rows=None, D=None, out_sum=None,
@@ -850,7 +850,7 @@ def bn_apply(x, mean, rstd, gamma, beta, act=None, p=0.0, seed=(None, 0), want_p
 
 
 def bn_vec_ok(x):
-    """bf16 channel-last rows with C % 8 == 0: the 16-byte BatchNorm kernels of csrc/convmod.hip apply (S2SVC_NO_BN_VEC=1: A/B switch)."""
+    """bf16 channel-last rows with C % 8 == 0: the 16-byte BatchNorm kernels of csrc/batchnorm.hip apply (S2SVC_NO_BN_VEC=1: A/B switch)."""
     return (x.dtype == torch.bfloat16 and x.shape[-1] % 8 == 0 and x.data_ptr() % 16 == 0 and x.numel() < 2 ** 31
             and os.environ.get("S2SVC_NO_BN_VEC", "0") != "1")
 

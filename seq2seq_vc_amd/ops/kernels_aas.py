@@ -4,9 +4,7 @@ import math
 import torch
 
 from .. import _lib
-from .kernels import _DT, dt, ptr, stream
-
-_WS_CHUNKS = 64
+from .kernels import _DT, _WS_CHUNKS, dt, ptr, stream
 
 
 def dwconv(x, w, bias, ks, dil=1, flip=False, add=None):
@@ -39,7 +37,7 @@ def convmod_supported(C, ks):
 
 def convmod_fwd(y2, w, bias, ks, eps, momentum, run_mean=None, run_var=None, num_batches=None, vlens=None):
     """Conformer convolution module core, bf16 training: y2 (B,T,2C) -> z = dwconv(glu(y2)) (B,T,C) and its batch statistics
-    (mean, rstd) in two launches (csrc/convmod.hip).  vlens (B int32, device): frames t >= vlens[b] are absent (include/s2svc_hip.h)."""
+    (mean, rstd) in two launches (csrc/convmod.hip; the second is the stage-2 finalize of csrc/batchnorm.hip).  vlens (B int32, device): frames t >= vlens[b] are absent (include/s2svc_hip.h)."""
     B, T, C2 = y2.shape
     C = C2 // 2
     z = torch.empty((B, T, C), dtype=y2.dtype, device=y2.device)

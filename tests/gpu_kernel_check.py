@@ -927,9 +927,9 @@ def batchnorm(dtype):
 
 @case
 def batchnorm_act_dropout_vectorised():
-    """The 16-byte BatchNorm + activation + dropout kernels of csrc/convmod.hip (bf16 training path of Fn.batch_norm_act: statistics,
+    """The 16-byte BatchNorm + activation + dropout kernels of csrc/batchnorm.hip (bf16 training path of Fn.batch_norm_act: statistics,
     apply, and a backward pass that recomputes the activation / dropout derivative) against torch fp32 (no dropout) and against the
-    scalar kernels of norm.hip with the same seeds => same dropout masks."""
+    scalar kernels of the same file with the same seeds => same dropout masks."""
     import os
     from seq2seq_vc_amd.ops import functional as Fn
     res = []

@@ -323,13 +323,9 @@ LEDGER = {
     "s2svc_dwconv": ("case", "gpu_kernel_check_aas", "depthwise_conv"),                       # = s2svc_dwconv_add with add = NULL
     "s2svc_add_head_bias_ld": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
     "s2svc_add_rows": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_bn_stats_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_bn_act_apply_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
-    "s2svc_bn_act_bwd_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_rstd_from_var": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_convmod_supported": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
-    "s2svc_convmod_fwd": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
-    "s2svc_convmod_bwd": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
     "s2svc_convmod_wgrad_final": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
     "s2svc_bn_swish_apply": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
     "s2svc_ln_act_fwd": ("case", "gpu_kernel_check_aas", "dds_half_layer_fused"),
