@@ -31,7 +31,7 @@ __global__ void bn_apply_kernel(int64_t total, int C, const T* __restrict__ x, c
     float v = (ldf(x + i) - mean[c]) * rstd[c] * gamma[c] + beta[c];
     if (pre_act) stf(pre_act + i, v);
     v = act_apply(v, act);
-    if (p > 0.f) v *= dropout_scale(seed, (uint64_t)i, p, inv_keep);
+    if (p > 0.f) v = drop_mul(v, dropout_scale(seed, (uint64_t)i, p, inv_keep));
     stf(y + i, v);
   }
 }
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void bn_act_apply_vec_kernel(int rows, int C, 
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       f[e] = act_apply(f[e], act);
-      if (p > 0.f) f[e] *= mk[e];
+      if (p > 0.f) f[e] = drop_mul(f[e], mk[e]);
     }
     *reinterpret_cast<uint4*>(y + o) = pack_bf16x8(f);
   }

@@ -157,6 +157,10 @@ __device__ __forceinline__ float dropout_scale(uint64_t seed, uint64_t idx, floa
   const uint32_t w = (uint32_t)(dropout_draw(seed, idx >> 2) >> ((idx & 3) * 16)) & 0xffffu;
   return w < dropout_threshold(p) ? 0.f : inv_keep;
 }
+// v * m for a kept element, +0 for a dropped one (m = 0): the bare product would carry the sign of v into the zero.  One fma, the
+// cost of the product: -0 + +0 is +0, and adding +0 changes nothing else.  Dropped, masked and absent outputs are +0 bit for bit in every
+// row-wise and element-wise kernel (tests/gpu_row_kernel_check.py holds them to it).
+__device__ __forceinline__ float drop_mul(float v, float m) { return __builtin_fmaf(v, m, 0.f); }
 
 // ---- 16-byte (8 x bf16 / 2 x 4 x fp32) register <-> memory helpers of the vectorised element-wise kernels ----
 __device__ __forceinline__ void unpack_bf16x8(const uint4& v, float (&f)[8]) {

@@ -17,7 +17,7 @@ __global__ void act_dropout_fwd_kernel(int64_t n, const T* __restrict__ x, int a
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   EW_LOOP(i, n) {
     float v = act_apply(ldf(x + i), act);
-    if (p > 0.f) v *= dropout_scale(seed, (uint64_t)i, p, inv_keep);
+    if (p > 0.f) v = drop_mul(v, dropout_scale(seed, (uint64_t)i, p, inv_keep));
     stf(y + i, v);
   }
 }
@@ -50,7 +50,7 @@ __global__ void act_dropout_bwd_kernel(int64_t n, const T* __restrict__ dz, cons
     } else {
       d = 1.f;
     }
-    stf(dx + i, ldf(dz + i) * m * d);
+    stf(dx + i, drop_mul(ldf(dz + i) * m, d));
   }
 }
 
@@ -67,7 +67,7 @@ __global__ void act_dropout_fwd_vec_kernel(int64_t n8, const bf16_t* __restrict_
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       v[e] = act_apply(v[e], act);
-      if (p > 0.f) v[e] *= m[e];
+      if (p > 0.f) v[e] = drop_mul(v[e], m[e]);
     }
     *reinterpret_cast<uint4*>(y + i * 8) = pack_bf16x8(v);
   }
@@ -84,7 +84,7 @@ __global__ void act_dropout_bwd_vec_kernel(int64_t n8, const bf16_t* __restrict_
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float mm = p > 0.f ? m[e] : 1.f;
-      g[e] = g[e] * mm * act_grad_from_saved(s[e], mm, act);
+      g[e] = drop_mul(g[e] * mm, act_grad_from_saved(s[e], mm, act));
     }
     *reinterpret_cast<uint4*>(dx + i * 8) = pack_bf16x8(g);
   }
@@ -105,7 +105,7 @@ __global__ void posenc_fwd_kernel(int64_t n, int Tlen, int D, const T* __restric
     const int t = (int)((i / D) % Tlen);
     float v = ldf(x + i) * xscale;
     if (pe) v += a * pe[(int64_t)t * D + d];
-    if (p > 0.f) v *= dropout_scale(seed, (uint64_t)i, p, inv_keep);
+    if (p > 0.f) v = drop_mul(v, dropout_scale(seed, (uint64_t)i, p, inv_keep));
     stf(y + i, v);
   }
 }
@@ -121,7 +121,7 @@ __global__ void posenc_bwd_kernel(int64_t n, int Tlen, int D, const T* __restric
     const int d = (int)(i % D);
     const int t = (int)((i / D) % Tlen);
     const float m = p > 0.f ? dropout_scale(seed, (uint64_t)i, p, inv_keep) : 1.f;
-    const float g = ldf(dy + i) * m;
+    const float g = drop_mul(ldf(dy + i), m);
     stf(dx + i, g * xscale);
     if (dalpha_partial) acc += g * pe[(int64_t)t * D + d];
   }

@@ -114,6 +114,13 @@ __global__ __launch_bounds__(256) void ln_fwd_reg_kernel(int rows, int D, const 
   }
 }
 
+// a * b rounded to float32 on its own, never fused into an addition behind it (hipcc contracts by default and honours this pragma;
+// __fmul_rn is a plain product to it)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // LayerNorm backward wrt the normalised input s (+ fused residual/dropout split):
 //   g = dy*gamma ; ds = rstd*(g - mean(g) - xhat*mean(g*xhat)) + ds_extra
 //   dres = ds ; dh = ds * dropmask
@@ -129,8 +136,10 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int D, const T* _
   const int64_t base = (int64_t)row * D;
   const float mu = mean[row], rs = rstd[row];
   float a = 0.f, b = 0.f;
+  // g = dy * gamma is formed twice, here and below: mul_rn keeps the compiler from fusing one of the two products into the add
+  // behind it.  Fused, g - mean(g) is the rounding error of a product where it should be 0 (a constant row, D = 1), times rstd = 1e6.
   for (int c = lane; c < D; c += 64) {
-    float g = ldf(dy + base + c) * gamma[c];
+    float g = mul_rn(ldf(dy + base + c), gamma[c]);
     float xh = (ldf(s + base + c) - mu) * rs;
     a += g;
     b += g * xh;
@@ -139,14 +148,14 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(int rows, int D, const T* _
   b = wave_sum(b) / (float)D;
   const float inv_keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
   for (int c = lane; c < D; c += 64) {
-    float g = ldf(dy + base + c) * gamma[c];
+    float g = mul_rn(ldf(dy + base + c), gamma[c]);
     float xh = (ldf(s + base + c) - mu) * rs;
     float v = rs * (g - a - xh * b);
     if (ds_extra) v += ldf(ds_extra + base + c);
     stf(ds + base + c, v);
     if (dh) {
       float m = p > 0.f ? dropout_scale(seed, (uint64_t)(base + c), p, inv_keep) : 1.f;
-      stf(dh + base + c, v * m * hscale);
+      stf(dh + base + c, drop_mul(v * m, hscale));
     }
   }
 }
@@ -294,7 +303,7 @@ __device__ __forceinline__ void ln_bwd_vec_row(int row, int D, const bf16_t* __r
         float m[8];
         if (p > 0.f) dropout_scale8(seed, (uint64_t)(base + c), p, inv_keep, m);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = v[e] * (p > 0.f ? m[e] : 1.f) * hscale;
+        for (int e = 0; e < 8; ++e) v[e] = drop_mul(v[e] * (p > 0.f ? m[e] : 1.f), hscale);
         *reinterpret_cast<uint4*>(dh + base + c) = pack_bf16x8(v);
       }
     }

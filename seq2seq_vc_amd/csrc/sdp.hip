@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256) void ln_act_fwd_kernel(int rows, int D, int Tn
     const int c = lane + 64 * i;
     if (c < D) {
       float o = act_apply((v[i] - mean) * rstd * gamma[c] + beta[c], act);
-      if (p > 0.f) o *= dropout_scale(seed, (uint64_t)(base + c), p, inv_keep);
+      if (p > 0.f) o = drop_mul(o, dropout_scale(seed, (uint64_t)(base + c), p, inv_keep));
       if (res) o += ldf(res + base + c);
       stf(y + base + c, ok ? o : 0.f);
     }
@@ -205,8 +205,8 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(int rows, int D, int Tn
       if (dres) stf(dres + base + c, d);
       xh[i] = (ldf(x + base + c) - mu) * rs;
       const float u = xh[i] * gamma[c] + beta[c];
-      float du = d * act_deriv(u, act);
-      if (p > 0.f) du *= dropout_scale(seed, (uint64_t)(base + c), p, inv_keep);
+      float du = drop_mul(d, act_deriv(u, act));          // (a masked row, d = 0, gives +0 whatever the sign of act')
+      if (p > 0.f) du = drop_mul(du, dropout_scale(seed, (uint64_t)(base + c), p, inv_keep));
       stf(du_out + base + c, du);
       g[i] = du * gamma[c];
       a += g[i];
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void ln_act_bwd_kernel(int rows, int D, int Tn
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = lane + 64 * i;
-    if (c < D) stf(dx + base + c, rs * (g[i] - a - xh[i] * b));
+    if (c < D) stf(dx + base + c, ok ? rs * (g[i] - a - xh[i] * b) : 0.f);
   }
 }
 

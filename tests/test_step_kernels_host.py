@@ -321,16 +321,10 @@ LEDGER = {
     "s2svc_hifigan_cin_padded": ("not a kernel", "host-side padding query of the vocoder's weight layout"),
     "s2svc_stft_logmel_fft_supported": ("not a kernel", "host-side size query of the STFT front-end"),
     "s2svc_dwconv": ("case", "gpu_kernel_check_aas", "depthwise_conv"),                       # = s2svc_dwconv_add with add = NULL
-    "s2svc_add_head_bias_ld": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_add_rows": ("case", "gpu_kernel_check_aas", "rel_attention_fused_vs_separate"),
-    "s2svc_bn_act_apply_vec": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_rstd_from_var": ("case", "gpu_kernel_check", "batchnorm_act_dropout_vectorised"),
     "s2svc_convmod_supported": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
     "s2svc_convmod_wgrad_final": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
     "s2svc_bn_swish_apply": ("case", "gpu_kernel_check_aas", "conformer_conv_module_fused"),
-    "s2svc_ln_act_fwd": ("case", "gpu_kernel_check_aas", "dds_half_layer_fused"),
-    "s2svc_ln_act_bwd": ("case", "gpu_kernel_check_aas", "dds_half_layer_fused"),
-    "s2svc_dw_ln_act_fwd": ("case", "gpu_kernel_check_aas", "dds_half_layer_fused"),
     "s2svc_embedding_fwd": ("case", "gpu_kernel_check_aas", "embedding_and_duration_loss"),
     "s2svc_embedding_bwd": ("case", "gpu_kernel_check_aas", "embedding_and_duration_loss"),
     "s2svc_duration_loss_fwd": ("case", "gpu_kernel_check_aas", "embedding_and_duration_loss"),
