@@ -20,10 +20,8 @@
 // product; the stored outputs.  Everything else is fp32.
 // Same output layout ((B, H, T1, ld), ld = T2 rounded up to 8, pad columns zero) and the same dropout masks (a function of the seed and
 // the element index in that layout) as softmax.hip / attn_fused.hip: forward and backward may come from different kernel families.
-#include "common.h"
-#include "../../include/s2svc_hip.h"
+#include "lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace {
@@ -55,9 +53,6 @@ typedef __attribute__((ext_vector_type(4))) short am_s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short am_s16x8_t;
 typedef __attribute__((address_space(3))) am_s16x4_t am_lds_s16x4_t;
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-template <int N> __device__ __forceinline__ void am_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // LDS image of a 32-wide operand slice (64-byte rows, lane-linear as the LDS-DMA instruction writes it) with the XOR swizzle of
 // gemm_glds.hip / relattn.hip on the per-lane SOURCE address and on the fragment read
 __device__ __forceinline__ int am_swz32(int r) { return (-(r >> 2)) & 3; }
@@ -150,7 +145,7 @@ __global__ __launch_bounds__(64 * NW) void attn_map_kernel(const am_args a) {
   int cur = 0;
 #pragma unroll 1
   for (int s = 0; s < nsteps; ++s) {
-    am_wait_vmcnt<4 + QI>();                          // slice s has landed (this wave's part); slice s + 1 may still be moving
+    wait_vmcnt<4 + QI>();                          // slice s has landed (this wave's part); slice s + 1 may still be moving
     __builtin_amdgcn_s_barrier();                     // ... for every wave; and everyone is done reading slice s - 1
     {
       int nxt = cur + 2;
@@ -169,7 +164,7 @@ __global__ __launch_bounds__(64 * NW) void attn_map_kernel(const am_args a) {
     }
     cur = cur + 1 == 3 ? 0 : cur + 1;
   }
-  am_wait_vmcnt<0>();                                // the copies issued past the end
+  wait_vmcnt<0>();                                // the copies issued past the end
   __syncthreads();                                   // operand slices are dead: LDS becomes the score tile
   // second product: its matrix (NT key rows x DK2, this head's columns) is fetched into registers NOW -- in the order of the LDS image it
   // will be written to once the tile is dead (1 KiB sub-tiles [32 keys][16 columns], the layout ds_read_b64_tr_b16 reads: gemm_glds.hip)

@@ -10,8 +10,8 @@
 // from zero, the runs added in order into a second register set): with T % 64 == 0 the steps are the 64-row K tiles of the split-K
 // GEMM this launch stands in for, the runs its split-K partials and their sum its reduction pass, MFMA for MFMA -- the same bits.
 // That equality is a property of the CALLER's choice of chunk_steps, and holds only while the replaced launches keep what it
-// mirrors: 64-row K tiles on the 16x16x32 bf16 MFMA with these fragment k positions (gemm_glds_kernel's TR operands), the
-// split-K plan, and splitk_reduce adding partials in ascending order.  The kernel itself promises the formula, the order stated
+// mirrors: 64-row K tiles on the 16x16x32 bf16 MFMA, the split-K plan, and splitk_reduce adding partials in ascending order.
+// (The fragment k positions are gemm_glds_kernel's TR operands' by construction: both read through tr_fragment_read, lds_dma.h.)  The kernel itself promises the formula, the order stated
 // here, and the rule of its check; tests/gpu_conv1d_wgrad_check.py fails when the plan or the route drifts.
 // Workgroups walk the units in order (u = blockIdx.x, += gridDim.x): the grid size changes which workgroup computes a unit,
 // never how, so the bits do not depend on the cap.
@@ -23,17 +23,11 @@
 // and nothing outside [0, T) of the utterance at hand is read from memory.  Both operands take the same permuted k positions of
 // a 32-frame half (4g..4g+3 and 16+4g..16+4g+3 for lane group g), which a product that sums over k does not see.
 // LDS: 4 * (2112 + 2240) = 17 408 bytes (single stage; the next step's rows wait in registers).
-#include "common.h"
-
-#include "../../include/s2svc_hip.h"
+#include "lds_dma.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
 
 constexpr int CW_MAX_ITEMS = 16;
 constexpr int CW_ROWS = 64;                 // frames per reduction step
@@ -65,11 +59,7 @@ struct cw_geom {
 
 // 8 frames of 16 channels, transposed: lane l of the wave gets channel (l & 15), frames k = 4g..4g+3 and 16+4g..16+4g+3 (g = l >> 4)
 __device__ __forceinline__ bf16x8_t cw_fragment(const char* img, int row0, int lane) {
-  const char* p = img + (row0 + (lane >> 4) * 4 + ((lane & 15) >> 2)) * 32 + (lane & 3) * 8;
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(p + 512));
-  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
+  return tr_fragment_read(img, row0, lane);
 }
 
 template <int KS>

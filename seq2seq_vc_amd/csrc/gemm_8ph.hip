@@ -28,20 +28,13 @@
 //     activation / dropout / residual / c_map, 16-byte stores).
 #include <cstring>
 #include "gemm_common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-__device__ __attribute__((aligned(16))) uint4 g_zero16_8ph = {0u, 0u, 0u, 0u};
-
 enum { P8_DENSE = 0, P8_CONV2D = 1, P8_TCONV2D = 2, P8_CONV1D = 3 };
 
-template <int N> __device__ __forceinline__ void p8_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void p8_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// XCD-aware tile order (see gemm_glds.hip: XCD x gets the x-th contiguous run of tile ids) -- and, within the run, tiles walk DOWN
+// XCD-aware tile order (xcd_contiguous_id: XCD x gets the x-th contiguous run of tile ids) -- and, within the run, tiles walk DOWN
 // groups of GH tile rows before they move to the next tile column, so that the ~32 workgroups an XCD runs side by side cover a
 // compact GH x (32 / GH) block of tiles instead of a strip of one or two tile rows: the rows of A and B that block pulls through
 // the XCD's L2 are GH * BM + (32 / GH) * BN instead of 2 * BM + 16 * BN (packed Q|K|V on 256 x 288 tiles: 3200 instead of 5120).
@@ -53,11 +46,7 @@ template <int BM, int BN, bool GROUPED = false>
 __device__ __forceinline__ void p8_tile_of_block(int& bm, int& bn) {
   const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy;
   int id = blockIdx.y * gx + blockIdx.x;
-  if (gridDim.z == 1 || (nwg & 7) == 0) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = id & 7, j = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  if (gridDim.z == 1 || (nwg & 7) == 0) id = xcd_contiguous_id(id, nwg);
   if (GROUPED && gx >= 4) {
     const int qe = (nwg >> 3) < 32 ? (nwg >> 3) : 32;              // workgroups of one XCD that run at the same time
     const int t2 = 2 * qe * BN / BM;
@@ -73,9 +62,6 @@ __device__ __forceinline__ void p8_tile_of_block(int& bm, int& bn) {
   bm = id / gx;
   bn = id - bm * gx;
 }
-
-// byte offset of (row r, piece slot for k piece c) inside a unit
-__device__ __forceinline__ int p8_off(int r, int c) { return r * 128 + ((c ^ ((r >> 1) & 7)) << 4); }
 
 // The scalar part of a source address: byte offset of K tile kt from the operand's base (added to the uniform base pointer).
 template <int KIND>
@@ -213,7 +199,7 @@ __device__ __forceinline__ int p8_rowmask_of(const s2svc_operand& o, int r, int 
 // still issued, from a zero block, so that the counted waits stay exact)
 template <int NI>
 __device__ __forceinline__ void p8_issue(const char* base, const uint32_t (&off)[NI], char* lds_unit, int wave_s) {
-  const char* b = base ? base : reinterpret_cast<const char*>(&g_zero16_8ph);
+  const char* b = base ? base : reinterpret_cast<const char*>(&g_zero16);
 #pragma unroll
   for (int e = 0; e < NI; ++e) {
     const uint32_t o = base ? off[e] : 0u;
@@ -226,7 +212,7 @@ __device__ __forceinline__ void p8_issue(const char* base, const uint32_t (&off)
 template <int NI>
 __device__ __forceinline__ void p8_issue_masked(const char* base, const uint32_t (&off)[NI], const int (&mask)[NI], int bit,
                                                 char* lds_unit, int wave_s) {
-  const char* z = reinterpret_cast<const char*>(&g_zero16_8ph);
+  const char* z = reinterpret_cast<const char*>(&g_zero16);
 #pragma unroll
   for (int e = 0; e < NI; ++e) {
     // (the select costs: the aligner's Conv1d 4096 x 1536 x 4608 takes 85.7 us with it and 68.6 us with no masking at all; a wave-uniform
@@ -268,7 +254,7 @@ __device__ __forceinline__ void p8_mfma(const bf16x8_t (&a)[NA][2], const bf16x8
 }
 
 #define P8_PHASE_SYNC_IN()                 \
-  p8_wait_lgkm0();                         \
+  wait_lgkm0();                         \
   __builtin_amdgcn_sched_barrier(0);       \
   __builtin_amdgcn_s_barrier();            \
   __builtin_amdgcn_sched_barrier(0)
@@ -363,7 +349,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_q(const s2svc_gemm_desc d
     p8_issue_a<KA, NIA>(a1, offA[1], mA[1], bit1, smem + BUF + OA1, wave);
     wa.next(d.A);
   }
-  p8_wait_vmcnt<2 * NIA + NIB>();
+  wait_vmcnt<2 * NIA + NIB>();
   __builtin_amdgcn_s_barrier();
   if (STAGGER && half == 1) __builtin_amdgcn_s_barrier();
 
@@ -397,7 +383,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_q(const s2svc_gemm_desc d
     // ---- phase 4: quadrant (m1, n0)   (fb0 is still live: B.n0 needs no second read, its unit died after phase 1 --
     //      it is nevertheless re-filled only in phase 1 of the next tile, keeping one unit per phase)
     p8_issue_a<KA, NIA>(a2, offA[1], mA[1], bit2, cur + OA1, wave);            // A.m1 of tile t + 2
-    p8_wait_vmcnt<2 * NIA + NIB>();                                           // everything of tile t + 1 has landed
+    wait_vmcnt<2 * NIA + NIB>();                                           // everything of tile t + 1 has landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb0, acc[1][0]);
     P8_PHASE_SYNC_OUT();
@@ -405,7 +391,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_q(const s2svc_gemm_desc d
     wb.next(d.A);
   }
   if (STAGGER && half == 0) __builtin_amdgcn_s_barrier();
-  p8_wait_vmcnt<0>();                  // the zero-block DMAs issued past the end
+  wait_vmcnt<0>();                  // the zero-block DMAs issued past the end
   __syncthreads();                     // every wave is done with the operand stages: reuse them as fp32 C tiles
   float* cs = reinterpret_cast<float*>(smem) + wave * (64 * 32);
   const bool cmap_lean = KA == P8_TCONV2D && d.tile_hint != 65 && epilogue_cmap_ok(d);      // uniform (tile_hint 65: A/B aid, the general flush)
@@ -487,7 +473,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_128(const s2svc_gemm_desc
     p8_issue<2>(has1 ? Bb + wa1.off_bytes_b(d.A) : nullptr, offB, smem + BUF + 2 * UNIT, wave);
     wa0.next(d.A);
   }
-  p8_wait_vmcnt<4>();                  // tile 0 has landed (A.m0, B of tile 1 may still be moving)
+  wait_vmcnt<4>();                  // tile 0 has landed (A.m0, B of tile 1 may still be moving)
   __builtin_amdgcn_s_barrier();
   if (STAGGER && wr == 1) __builtin_amdgcn_s_barrier();
 
@@ -499,7 +485,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_128(const s2svc_gemm_desc
     p8_read<2>(cur + 2 * UNIT, rdB, p0, p1, fb);
     p8_read<4>(cur + 0 * UNIT, rdA, p0, p1, fa);
     p8_issue_a<KA, 2>((t + 1 < nt) ? Ab + wa1.off_bytes(d.A) : nullptr, offA[1], mA[1], wa1.bit(), oth + 1 * UNIT, wave);     // A.m1 of tile t + 1
-    p8_wait_vmcnt<6>();                                                                             // A.m1 of tile t has landed
+    wait_vmcnt<6>();                                                                             // A.m1 of tile t has landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb, acc[0]);
     P8_PHASE_SYNC_OUT();
@@ -507,7 +493,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_128(const s2svc_gemm_desc
     p8_read<4>(cur + 1 * UNIT, rdA, p0, p1, fa);
     p8_issue_a<KA, 2>((t + 2 < nt) ? Ab + wa0.off_bytes(d.A) : nullptr, offA[0], mA[0], wa0.bit(), cur + 0 * UNIT, wave);     // A.m0 of tile t + 2
     p8_issue<2>((t + 2 < nt) ? Bb + wa0.off_bytes_b(d.A) : nullptr, offB, cur + 2 * UNIT, wave);      // B of tile t + 2
-    p8_wait_vmcnt<6>();                                                                             // A.m0, B of tile t + 1 have landed
+    wait_vmcnt<6>();                                                                             // A.m0, B of tile t + 1 have landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb, acc[1]);
     P8_PHASE_SYNC_OUT();
@@ -515,7 +501,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_128(const s2svc_gemm_desc
     wa1.next(d.A);
   }
   if (STAGGER && wr == 0) __builtin_amdgcn_s_barrier();
-  p8_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   float* cs = reinterpret_cast<float*>(smem) + wave * (64 * 32);
   const bool cmap_lean = KA == P8_TCONV2D && d.tile_hint != 65 && epilogue_cmap_ok(d);      // uniform
@@ -592,7 +578,6 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_n96(const s2svc_gemm_desc
 
 #define N96_A(T, BUFP) p8_issue<4>((T) < nt ? Ab + (int64_t)(T) * 128 : nullptr, offA, (BUFP), wave)
 #define N96_B(T, P, BUFP) p8_issue<2>(((T) < nt && bwave) ? Bb + (int64_t)(T) * 128 : nullptr, offB[P], (BUFP) + UA + (P) * UB, wave)
-#define N96_WAIT(N, A_DUE) p8_wait_vmcnt<(N)>()
   // prologue, in the order of the steady state: tile 0, then of tile 1 everything but its last B unit
   N96_A(0, smem);
 #pragma unroll
@@ -601,7 +586,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_n96(const s2svc_gemm_desc
 #pragma unroll
   for (int p = 0; p + 1 < PH; ++p) N96_B(1, p, smem + BUF);
   // A + B.0 of tile 0 have landed: what was issued behind them may still be moving
-  N96_WAIT(PH == 2 ? 8 : 12, true);
+  wait_vmcnt<(PH == 2 ? 8 : 12)>();
   __builtin_amdgcn_s_barrier();
   if (STAGGER && half == 1) __builtin_amdgcn_s_barrier();
 
@@ -613,7 +598,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_n96(const s2svc_gemm_desc
     p8_read<3>(cur + UA, rdB, p0, p1, fb);
     p8_read<4>(cur, rdA, p0, p1, fa);
     N96_B(t + 1, PH - 1, oth);                              // the last B unit of tile t + 1 (read in the last phase of tile t - 1)
-    N96_WAIT(PH == 2 ? 8 : 12, false);                      // B.1 of tile t has landed
+    wait_vmcnt<(PH == 2 ? 8 : 12)>();                      // B.1 of tile t has landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 3>(fa, fb, acc[0]);
     P8_PHASE_SYNC_OUT();
@@ -621,7 +606,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_n96(const s2svc_gemm_desc
     p8_read<3>(cur + UA + UB, rdB, p0, p1, fb);
     N96_A(t + 2, cur);                                      // A, B.0 of tile t + 2
     N96_B(t + 2, 0, cur);
-    N96_WAIT(PH == 2 ? 8 : 16, PH == 2);                    // PH = 2: A, B.0 of tile t + 1; PH = 3: B.2 of tile t
+    wait_vmcnt<(PH == 2 ? 8 : 16)>();                    // PH = 2: A, B.0 of tile t + 1; PH = 3: B.2 of tile t
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 3>(fa, fb, acc[1]);
     P8_PHASE_SYNC_OUT();
@@ -629,17 +614,16 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel_n96(const s2svc_gemm_desc
       // ---- phase 2
       p8_read<3>(cur + UA + 2 * UB, rdB, p0, p1, fb);
       N96_B(t + 2, 1, cur);                                 // B.1 of tile t + 2
-      N96_WAIT(12, true);                                   // A, B.0 of tile t + 1
+      wait_vmcnt<12>();                                   // A, B.0 of tile t + 1
       P8_PHASE_SYNC_IN();
       p8_mfma<4, 3>(fa, fb, acc[PH - 1]);
       P8_PHASE_SYNC_OUT();
     }
   }
-#undef N96_WAIT
 #undef N96_A
 #undef N96_B
   if (STAGGER && half == 0) __builtin_amdgcn_s_barrier();
-  p8_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   float* cs = reinterpret_cast<float*>(smem) + wave * (64 * 32);
   const int mw = m0 + wr * 64, nw = n0 + wc * WN;
@@ -775,7 +759,7 @@ __device__ __forceinline__ void p8_tr_tile(const s2svc_gemm_desc& d, int tile_m,
     p8_issue<2>(has1 ? Ab + stepA : nullptr, offA[0], smem + BUF + 0 * UNIT, wave);
     p8_issue<2>(has1 ? Bb + stepB : nullptr, offB, smem + BUF + 2 * UNIT, wave);
   }
-  p8_wait_vmcnt<4>();                  // tile 0 has landed (A.m0, B of tile 1 may still be moving)
+  wait_vmcnt<4>();                  // tile 0 has landed (A.m0, B of tile 1 may still be moving)
   __builtin_amdgcn_s_barrier();
   if (STAGGER && wr == 1) __builtin_amdgcn_s_barrier();
 
@@ -788,7 +772,7 @@ __device__ __forceinline__ void p8_tr_tile(const s2svc_gemm_desc& d, int tile_m,
     p8_read_tr<2>(cur + 2 * UNIT, foB, fb);
     p8_read_tr<4>(cur + 0 * UNIT, foA, fa);
     p8_issue<2>((t + 1 < nt) ? Ab + (int64_t)(t + 1) * stepA : nullptr, offA[1], oth + 1 * UNIT, wave);     // A.m1 of tile t + 1
-    p8_wait_vmcnt<6>();                                                                              // A.m1 of tile t has landed
+    wait_vmcnt<6>();                                                                              // A.m1 of tile t has landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb, acc[0]);
     if (do_rowsum && mine < 2) {
@@ -800,7 +784,7 @@ __device__ __forceinline__ void p8_tr_tile(const s2svc_gemm_desc& d, int tile_m,
     p8_read_tr<4>(cur + 1 * UNIT, foA, fa);
     p8_issue<2>((t + 2 < nt) ? Ab + (int64_t)(t + 2) * stepA : nullptr, offA[0], cur + 0 * UNIT, wave);     // A.m0 of tile t + 2
     p8_issue<2>((t + 2 < nt) ? Bb + (int64_t)(t + 2) * stepB : nullptr, offB, cur + 2 * UNIT, wave);        // B of tile t + 2
-    p8_wait_vmcnt<6>();                                                                              // A.m0, B of tile t + 1 have landed
+    wait_vmcnt<6>();                                                                              // A.m0, B of tile t + 1 have landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb, acc[1]);
     if (do_rowsum && mine < 2) {
@@ -810,7 +794,7 @@ __device__ __forceinline__ void p8_tr_tile(const s2svc_gemm_desc& d, int tile_m,
     P8_PHASE_SYNC_OUT();
   }
   if (STAGGER && wr == 0) __builtin_amdgcn_s_barrier();
-  p8_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   if (do_rowsum) {
     // every column of rs[a][i] holds the partial sums of rows (a, i, lg * 4 + r): column lr == 0 writes them, then one thread
@@ -905,7 +889,7 @@ __device__ __forceinline__ void p8_tr_tile_q(const s2svc_gemm_desc& d, int tile_
     p8_issue<2>(has1 ? Bb + stepB : nullptr, offB[1], smem + BUF + OB1, wave);
     p8_issue<2>(has1 ? Ab + stepA : nullptr, offA[1], smem + BUF + OA1, wave);
   }
-  p8_wait_vmcnt<6>();
+  wait_vmcnt<6>();
   __builtin_amdgcn_s_barrier();
   if (STAGGER && half == 1) __builtin_amdgcn_s_barrier();
 
@@ -942,7 +926,7 @@ __device__ __forceinline__ void p8_tr_tile_q(const s2svc_gemm_desc& d, int tile_
     P8_PHASE_SYNC_OUT();
     // ---- phase 4: quadrant (m1, n0)
     p8_issue<2>(a2, offA[1], cur + OA1, wave);                                // A.m1 of tile t + 2
-    p8_wait_vmcnt<6>();                                                       // everything of tile t + 1 has landed
+    wait_vmcnt<6>();                                                       // everything of tile t + 1 has landed
     P8_PHASE_SYNC_IN();
     p8_mfma<4, 2>(fa, fb0, acc[1][0]);
     if (do_rowsum && mine < 2) {
@@ -952,7 +936,7 @@ __device__ __forceinline__ void p8_tr_tile_q(const s2svc_gemm_desc& d, int tile_
     P8_PHASE_SYNC_OUT();
   }
   if (STAGGER && half == 0) __builtin_amdgcn_s_barrier();
-  p8_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __syncthreads();
   if (do_rowsum) {
     float* part = reinterpret_cast<float*>(smem + 2 * BUF - 4096);
@@ -993,22 +977,15 @@ __global__ __launch_bounds__(512) void gemm_8ph_tr_kernel(const s2svc_gemm_desc 
   p8_tr_tile<STAGGER>(d, tile_m, tile_n, smem);
 }
 
-// Grouped launch (see gemm_grouped_kernel, gemm_glds.hip): the weight gradients of a few consecutive layers as ONE grid of
-// 256 x 128 tiles, descriptors by value in the kernel arguments.
-#define P8_GROUP_MAX 10
-struct p8_group_args {
-  s2svc_gemm_desc d[P8_GROUP_MAX];
-  int32_t tile_start[P8_GROUP_MAX + 1];
-  int32_t n;
-};
-static_assert(sizeof(p8_group_args) <= 4096, "kernel arguments are limited to 4 KB");
+// Grouped launch (group_args, lds_dma.h; see gemm_grouped_kernel, gemm_glds.hip): the weight gradients of a few consecutive
+// layers as ONE grid of 256 x 128 tiles.
 
 template <bool STAGGER, int BN>
-__global__ __launch_bounds__(512) void gemm_8ph_tr_grouped_kernel(const p8_group_args g) {
+__global__ __launch_bounds__(512) void gemm_8ph_tr_grouped_kernel(const group_args g) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * (BN == 256 ? 4 : 3) * 16384];
-  int p = 0;
+  int p = 0;                                              // tile_start[p] <= blockIdx.x < tile_start[p + 1]
 #pragma unroll
-  for (int i = 1; i < P8_GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
+  for (int i = 1; i < GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
   const s2svc_gemm_desc& d = g.d[p];
   const int t = (int)blockIdx.x - g.tile_start[p];
   const int tiles_n = d.N / BN;
@@ -1155,7 +1132,7 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
       }
     }
     const char* Bx = reinterpret_cast<const char*>(q.B);
-    const char* z = reinterpret_cast<const char*>(&g_zero16_8ph);
+    const char* z = reinterpret_cast<const char*>(&g_zero16);
     // the 12 DMA instructions of this loader for chunk-relative K tile T into stage T % 3
 #define W8LS_ISSUE(T)                                                                                                         \
     {                                                                                                                         \
@@ -1187,18 +1164,18 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
     }
     W8LS_ISSUE(0);
     W8LS_ISSUE(1);
-    p8_wait_vmcnt<12>();               // this loader's share of tile 0 has landed
+    wait_vmcnt<12>();               // this loader's share of tile 0 has landed
     __builtin_amdgcn_s_barrier();      // B(0)
 #pragma unroll 1
     for (int t = 0; t < nt; ++t) {
       W8LS_ISSUE(t + 2);               // stage (t + 2) % 3 = (t - 1) % 3: every consumer retired its reads of tile t - 1 before B(t)
-      p8_wait_vmcnt<12>();             // tile t + 1 has landed
+      wait_vmcnt<12>();             // tile t + 1 has landed
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();    // B(t + 1)
       __builtin_amdgcn_sched_barrier(0);
     }
 #undef W8LS_ISSUE
-    p8_wait_vmcnt<0>();                // (the zero-block DMAs issued past the end)
+    wait_vmcnt<0>();                // (the zero-block DMAs issued past the end)
     __builtin_amdgcn_s_barrier();      // the consumers' barrier in front of the epilogue: the stages become C tiles
     if (do_rowsum) __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_s_barrier();      // end of the unit (the consumers' epilogue has left the stages)
@@ -1237,7 +1214,7 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
     if (live0) {
       p8_read_tr<2>(st + 2 * UNIT, foB, fb);
       p8_read_tr<4>(st + 0 * UNIT, foA, fa);
-      p8_wait_lgkm0();
+      wait_lgkm0();
       __builtin_amdgcn_sched_barrier(0);
       p8_mfma<4, 2>(fa, fb, acc[0]);
       if (do_rowsum && mine < 2) {
@@ -1248,7 +1225,7 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
     }
     if (live1) {
       p8_read_tr<4>(st + 1 * UNIT, foA, fa);
-      p8_wait_lgkm0();
+      wait_lgkm0();
       __builtin_amdgcn_sched_barrier(0);
       p8_mfma<4, 2>(fa, fb, acc[1]);
       if (do_rowsum && mine < 2) {
@@ -1272,7 +1249,7 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
 #pragma unroll
           for (int r = 0; r < 4; ++r) part[wc * 256 + wr * 128 + a * 64 + i * 16 + lg * 4 + r] = rs[a][i][r];
     }
-    p8_wait_lgkm0();                                     // the partial sums are in LDS
+    wait_lgkm0();                                     // the partial sums are in LDS
     __builtin_amdgcn_s_barrier();
     if (threadIdx.x < 256) {
       const int m = m0 + (int)threadIdx.x;
@@ -1290,7 +1267,7 @@ __device__ __forceinline__ void w8ls_tile(const w8_prob& q, const w8_conv& cv, i
     else epilogue_stage<64, 32>(acc[1], cs);
     w8_flush(q, chunk, m0 + wr * 128 + a * 64, n0 + wc * 32, cs);
   }
-  p8_wait_lgkm0();
+  wait_lgkm0();
   __builtin_amdgcn_s_barrier();        // end of the unit: a further unit's DMAs may overwrite the C tiles
 }
 
@@ -1301,11 +1278,7 @@ __global__ __launch_bounds__(768) void gemm_w8ls_kernel(const w8_args g) {
 #pragma unroll 1
   for (int id = (int)blockIdx.x; id < g.total; id += (int)gridDim.x) {
     int u = id;
-    if (gridDim.x == (unsigned)g.total) {                // XCD x gets the x-th contiguous run of units
-      const int q8 = g.total >> 3, r8 = g.total & 7;
-      const int xcd = id & 7, j = id >> 3;
-      u = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    if (gridDim.x == (unsigned)g.total) u = xcd_contiguous_id(id, g.total);     // XCD x gets the x-th contiguous run of units
     int p = 0;
 #pragma unroll 1
     for (int i = 1; i < g.n; ++i) p += (g.unit_start[i] <= u) ? 1 : 0;
@@ -1380,8 +1353,6 @@ bool p8_tr_ok(const s2svc_gemm_desc& d) {      // exact tiles of dense row-conti
   if (d.emask || d.drop_p > 0.f || d.c_map || d.c_pre) return false;
   return true;
 }
-
-constexpr int p8_tr_mode() { return 1; }     // weight gradients on the 8-wave kernels (the 4-wave path was the A/B alternative through round 5)
 
 int g_p8_mode = -1;
 int p8_mode() {       // s2svc_gemm_set_8ph: 0 = off, 1 = on (default), 2 = on without the half-phase skew of the wave halves
@@ -1459,7 +1430,7 @@ extern "C" int s2svc_gemm_set_8ph(int mode) {
 extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
   const s2svc_gemm_desc& d = *desc;
   const int mode = p8_mode();
-  if (mode != 0 && p8_tr_mode() && d.tile_hint != 64 && p8_tr_ok(d) && (int64_t)(d.M / 256) * (d.N / 128) >= p8_min_tiles()) {
+  if (mode != 0 && d.tile_hint != 64 && p8_tr_ok(d) && (int64_t)(d.M / 256) * (d.N / 128) >= p8_min_tiles()) {
     const int64_t t128 = (int64_t)(d.M / 256) * (d.N / 128);
     if (p8_tr_take_q(d.N % 256 == 0, t128 / 2, t128)) {
       dim3 grid((unsigned)(d.N / 256), (unsigned)(d.M / 256), 1);
@@ -1513,8 +1484,7 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
   if (d.A.mode == S2SVC_OP_CONV1D) {
     // Conv1d as an implicit GEMM (the aligner's 1536 -> 1536 k3 layer over 4096 frames: 58 GF forward and data gradient, 0.24-0.28 of the
     // peak on the 4-wave kernel): the common epilogue only, one problem
-    static const bool c1d_on = true;
-    if (!c1d_on || mode != 1 || nb != 1 || !epilogue_common_ok(d)) return 0;
+    if (mode != 1 || nb != 1 || !epilogue_common_ok(d)) return 0;
     const int bm1 = geo == 2 ? 512 : 256, bn1 = geo == 1 ? 256 : 128;
     dim3 grid1((unsigned)((d.N + bn1 - 1) / bn1), (unsigned)((d.M + bm1 - 1) / bm1), 1);
     s2s_gemm_route(geo == 1 ? "8ph_q<CONV1D,2,4>" : geo == 2 ? "8ph_q<CONV1D,4,2>" : "8ph_128<CONV1D,lean>");
@@ -1541,13 +1511,12 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
       else hipLaunchKernelGGL((KERNEL<P8_DENSE, ##__VA_ARGS__, true>), grid, dim3(512), 0, st, d);        \
     }                                                                                                     \
   } while (0)
-  static const bool lean_on = true;
-  if (lean_on && !conv && !tconv && mode != 2 && epilogue_common_ok(d)) {       // dense operands + the common epilogue: lean variants
+  if (!conv && !tconv && mode != 2 && epilogue_common_ok(d)) {       // dense operands + the common epilogue: lean variants
     s2s_gemm_route(geo == 1 ? "8ph_q<DENSE,2,4,lean>" : geo == 2 ? "8ph_q<DENSE,4,2,lean>" : "8ph_128<DENSE,lean>");
     if (geo == 1) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_DENSE, 2, 4, true, true>), grid, dim3(512), 0, st, d);
     else if (geo == 2) hipLaunchKernelGGL((gemm_8ph_kernel_q<P8_DENSE, 4, 2, true, true>), grid, dim3(512), 0, st, d);
     else hipLaunchKernelGGL((gemm_8ph_kernel_128<P8_DENSE, true, 1>), grid, dim3(512), 0, st, d);
-  } else if (lean_on && geo == 3 && !conv && !tconv && mode != 2 && epilogue_swish_ok(d)) {        // the Conformer feed-forward pair
+  } else if (geo == 3 && !conv && !tconv && mode != 2 && epilogue_swish_ok(d)) {        // the Conformer feed-forward pair
     s2s_gemm_route("8ph_128<DENSE,swish>");
     hipLaunchKernelGGL((gemm_8ph_kernel_128<P8_DENSE, true, 2>), grid, dim3(512), 0, st, d);
   } else if (geo == 1) P8_LAUNCH("8ph_q<", ",2,4", gemm_8ph_kernel_q, 2, 4);
@@ -1566,8 +1535,8 @@ extern "C" int s2svc_gemm_try_8ph(const s2svc_gemm_desc* desc, void* stream) {
 // on the group -- it changes the schedule, not the order of any sum.
 extern "C" int s2svc_gemm_grouped_try_8ph(const s2svc_gemm_desc* descs, int n, void* stream) {
   const int mode = p8_mode();
-  if (mode == 0 || !p8_tr_mode() || n <= 0 || n > P8_GROUP_MAX) return 0;
-  p8_group_args g;
+  if (mode == 0 || n <= 0 || n > GROUP_MAX) return 0;
+  group_args g;
   std::memset(&g, 0, sizeof(g));
   int64_t t128 = 0, t256 = 0;
   bool all256 = true;
@@ -1590,7 +1559,7 @@ extern "C" int s2svc_gemm_grouped_try_8ph(const s2svc_gemm_desc* descs, int n, v
     g.tile_start[i] = (int32_t)total;
     total += (int64_t)(g.d[i].M / 256) * (g.d[i].N / (q ? 256 : 128));
   }
-  for (int i = m; i <= P8_GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
+  for (int i = m; i <= GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
   hipStream_t st = (hipStream_t)stream;
   if (q) {
     if (mode == 2) hipLaunchKernelGGL((gemm_8ph_tr_grouped_kernel<false, 256>), dim3((unsigned)total), dim3(512), 0, st, g);
@@ -1619,13 +1588,13 @@ int w8_kt_chunk_env() {   // s2svc_gemm_set_w8(., kt): K tiles (of 64 rows) per 
 // are cut by K.  Chunk length 64 K tiles (4096 rows): measured in the steps -- VTN's 2016 / 2048-row reductions are one chunk at 32 or 64
 // (3.80 ms either way; 16 / 8 / 4: 3.87 / 3.94 / 4.10), AAS-VC's 4096-row reductions run unsplit at 64 (11.47 vs 11.68 ms at 32: no
 // partial tiles, no reduction launch; 128: the same)
+constexpr int W8_CONV_KT_CHUNK = 75;      // K tiles per chunk of the Conv2d weight gradient (measured: see w8_chunks)
 void w8_chunks(int M, int N, int K, int& nchunks, int& kt_chunk, bool conv = false) {
   const int ktiles = (K + 63) / 64;
   if (conv) {       // the Conv2d weight gradient: a long reduction (tens of thousands of pixels) over ~50 tiles.  VTN's 384 x 3456 over 38304
     // pixels, stand-alone: chunks of 64 / 75 / 86 / 100 / 120 / 150 / 200 K tiles = 182 / 145 / 165 / 184 / 201 / 153 / 196 us (the 4-wave split-K
     // kernel: 152); the VTN step is the same for all of them (3.65-3.67 ms) -- 75
-    static const int ck = 75;
-    kt_chunk = ck < 1 ? 1 : ck;
+    kt_chunk = W8_CONV_KT_CHUNK;
     nchunks = (ktiles + kt_chunk - 1) / kt_chunk;
     return;
   }
@@ -1642,7 +1611,7 @@ void w8_chunks(int M, int N, int K, int& nchunks, int& kt_chunk, bool conv = fal
   }
 }
 bool w8_ok(const s2svc_gemm_desc& d) {
-  if (p8_mode() == 0 || !p8_tr_mode() || !w8_mode()) return false;
+  if (p8_mode() == 0 || !w8_mode()) return false;
   if (d.dtype != S2S_BF16 || d.c_dtype != S2S_F32 || d.nb0 * d.nb1 != 1 || d.splitk > 1) return false;
   if (d.A.layout != S2SVC_LAYOUT_RC || d.B.layout != S2SVC_LAYOUT_RC || d.A.mode != S2SVC_OP_DENSE) return false;
   const bool convB = d.B.mode == S2SVC_OP_CONV2D_S2;         // the Conv2d 3x3 stride 2 weight gradient: B = implicit im2col of the layer's input
@@ -1652,14 +1621,12 @@ bool w8_ok(const s2svc_gemm_desc& d) {
   if (((uintptr_t)d.A.ptr) % 16 || ((uintptr_t)d.B.ptr) % 16 || d.A.ld % 8 || d.B.ld % 8 || d.A.ld < d.M) return false;
   if ((int64_t)64 * d.A.ld * 2 + (int64_t)d.M * 2 >= (1ll << 32)) return false;
   if (convB) {
-    static const bool conv_on = true;
-    if (!conv_on || d.B.C < 128 || d.B.C % 128 || d.N != 9 * d.B.C || d.B.ld < d.B.C) return false;
+    if (d.B.C < 128 || d.B.C % 128 || d.N != 9 * d.B.C || d.B.ld < d.B.C) return false;
     if (d.B.T1 <= 0 || d.B.F1 <= 0 || d.B.T2 <= 0 || d.B.F2 <= 0 || 2 * (d.B.T2 - 1) + 3 > d.B.T1 || 2 * (d.B.F2 - 1) + 3 > d.B.F1) return false;
     if (d.K % (d.B.T2 * d.B.F2)) return false;               // whole images
     if ((int64_t)(d.K + 64) * (d.B.T2 * d.B.F2) >= (1ll << 32)) return false;       // the multiply-high divisions are exact below that
   } else if (conv1B) {
-    static const bool conv1_on = true;
-    if (!conv1_on || d.B.C < 128 || d.B.C % 128 || d.B.pad < 0 || d.N != (2 * d.B.pad + 1) * d.B.C || d.B.ld < d.B.C) return false;
+    if (d.B.C < 128 || d.B.C % 128 || d.B.pad < 0 || d.N != (2 * d.B.pad + 1) * d.B.C || d.B.ld < d.B.C) return false;
     if (d.B.T <= 0 || d.K % d.B.T) return false;             // whole utterances
     if ((int64_t)(d.K + 64) * d.B.T >= (1ll << 32)) return false;
     if ((int64_t)((d.M + 255) / 256) * ((d.N + 127) / 128) < 64) return false;       // few tiles (the Postnet's 256 x 1280): the split-K 4-wave kernel
@@ -1668,10 +1635,8 @@ bool w8_ok(const s2svc_gemm_desc& d) {
   }
   if (((uintptr_t)d.C) % 16 || d.ldc % 4 || d.ldc < d.N) return false;
   if (d.bias || d.res || d.act != S2S_ACT_NONE || d.alpha != 1.0f || d.emask || d.drop_p > 0.f || d.c_map || d.c_pre) return false;
-  // the exact-256 problems with >= 64 tiles of 128 x 128 (AAS-VC's decoder) ran on p8_tr_tile / p8_tr_tile_q until the loader-
-  // specialised tile beat both per flop (0.83 us per 256 x 128 K tile against 1.05)
-  static const bool exact_too = true;
-  if (!exact_too && w8_mode() != 2 && p8_tr_ok(d) && (int64_t)(d.M / 128) * (d.N / 128) >= 64) return false;
+  // (the exact-256 problems with >= 64 tiles of 128 x 128 -- AAS-VC's decoder -- come here too: the loader-specialised tile beats
+  // p8_tr_tile / p8_tr_tile_q per flop, 0.83 us per 256 x 128 K tile against 1.05)
   return true;
 }
 int64_t w8_ws_floats(const s2svc_gemm_desc& d) {
@@ -1716,8 +1681,7 @@ extern "C" int s2svc_gemm_wgrad_grouped_bg(const s2svc_gemm_desc* descs, int n, 
   S2S_REQUIRE(descs && n > 0, "gemm_wgrad_grouped: bad args");
   hipStream_t st = (hipStream_t)stream;
   const int mode = p8_mode();
-  static const int cap_env = 0;
-  const int cap = wgs_cap > 0 ? wgs_cap : cap_env;
+  const int cap = wgs_cap > 0 ? wgs_cap : 0;
   int64_t ws_off = 0;
   for (int i0 = 0; i0 < n; i0 += W8_MAX) {
     const int cnt = (n - i0 < W8_MAX) ? n - i0 : W8_MAX;

@@ -1,4 +1,5 @@
-// Shared by the MFMA GEMM kernels (gemm_fast.hip, gemm_skinny.hip): fragment types and the output epilogue.
+// Shared by the MFMA GEMM kernels (gemm_fast.hip, gemm_skinny.hip, gemm_glds.hip, gemm_8ph.hip; also gemm.hip, decode.hip and
+// hifigan_tile.h): fragment types and the output epilogue.
 #pragma once
 #include "common.h"
 #include "../../include/s2svc_hip.h"

@@ -316,7 +316,6 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(const s2svc_gemm_desc d)
 template <typename T, int BM, int BN, int BK>
 void launch_modes(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   const bool arc = d.A.layout == S2SVC_LAYOUT_RC, brc = d.B.layout == S2SVC_LAYOUT_RC;
-  static const bool lean_on = true;
   // the instantiations of s2svc_gemm_try_fast, by name (s2svc_gemm_last_route); MODES: the operand layouts and the epilogue
   static_assert(sizeof(T) == 4 ? ((BM == 128 && BK == 32) || (BM == 64 && BK == 64) || (BM == 32 && BK == 128)) : ((BM == 128 && BK == 64) || (BM == 64 && BK == 128)),
                 "a new instantiation needs a route name");
@@ -325,7 +324,7 @@ void launch_modes(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
                                 : (BM == 128 ? "fast<bf16,128,128,64," MODES ">" : "fast<bf16,64,64,128," MODES ">"))
 #define S2S_FAST_ROUTE_LEAN(MODES) s2s_gemm_route(BM == 64 ? "fast<f32,64,64,64," MODES ",lean>" : "fast<f32,32,32,128," MODES ",lean>")
   if constexpr (sizeof(T) == 4 && BM <= 64) {
-    if (lean_on && d.A.mode == S2SVC_OP_DENSE && d.B.mode == S2SVC_OP_DENSE && epilogue_common32_ok(d)) {
+    if (d.A.mode == S2SVC_OP_DENSE && d.B.mode == S2SVC_OP_DENSE && epilogue_common32_ok(d)) {
       if (!arc && !brc) { S2S_FAST_ROUTE_LEAN("KC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_KC, true>), grid, dim3(256), 0, st, d); }
       else if (!arc && brc) { S2S_FAST_ROUTE_LEAN("KC,RC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_KC, AM_RC, true>), grid, dim3(256), 0, st, d); }
       else if (arc && !brc) { S2S_FAST_ROUTE_LEAN("RC,KC"); hipLaunchKernelGGL((gemm_fast_kernel<float, BM, BN, BK, AM_RC, AM_KC, true>), grid, dim3(256), 0, st, d); }
@@ -382,10 +381,9 @@ extern "C" int s2svc_gemm_try_fast(const s2svc_gemm_desc* desc, void* stream) {
     // 96 workgroups; its 29-column spline projection: 16) take 32 x 32 tiles with K tiles of 128: the fp32 MFMA
     // (v_mfma_f32_16x16x4f32, 256 flop / clk / CU) makes a 64 x 64 x 384 workgroup 5 us of matrix-pipe time on its own;
     // a quarter of it per workgroup, on four times the workgroups.  Same order of every sum (k ascending), same bits.
-    static const bool t32_on = true;
     const int64_t tiles64 = (int64_t)((d.M + 63) / 64) * ((d.N + 63) / 64) * d.nb0 * d.nb1 * splitk;
     const bool t32_ok = d.dtype == S2S_F32 && d.K >= 128 && d.A.mode == S2SVC_OP_DENSE && d.B.mode == S2SVC_OP_DENSE;
-    if (t32_ok && ((t32_on && d.tile_hint == 0 && tiles64 < 128 && !d.a_rowsum) || d.tile_hint == 32)) {      // (hint 32: ops.kernels.plan_gemm)
+    if (t32_ok && ((d.tile_hint == 0 && tiles64 < 128 && !d.a_rowsum) || d.tile_hint == 32)) {      // (hint 32: ops.kernels.plan_gemm)
       dim3 grid((d.N + 31) / 32, (d.M + 31) / 32, d.nb0 * d.nb1 * splitk);
       launch_modes<float, 32, 32, 128>(d, grid, st);
     } else {

@@ -8,52 +8,33 @@
 //     (rows r..r+15 at pieces c / c^1) hits 16 distinct 16-byte bank slots.
 //   * Row-contiguous operands (activations in wgrad, weights in dgrad) are DMA-ed k-major into LDS and their fragments
 //     come from ds_read_b64_tr_b16 transpose reads (TrStage / tr_fragment below); a K-contiguous partner then reads the
-//     same permuted k positions with two ds_read_b64 (kc_fragment_perm).  The register-transpose path (RcStage: 8x8
-//     blocks, v_perm_b32, ds_write_b128 into the swizzled image) remains in the file for operands the transpose read cannot take.
-//   * Two LDS buffers: tile t+1 is in flight (DMA + global loads) while the MFMAs consume tile t; one barrier per
-//     K tile.  Pieces outside the matrix / the conv input are fetched from a 16-byte zero block.
+//     same permuted k positions with two ds_read_b64 (kc_fragment_perm).  Every operand is staged by DMA: no kernel
+//     of this file moves a tile through registers.
+//   * Two LDS buffers: tile t+1 is in flight while the MFMAs consume tile t; one barrier per K tile (the all-DMA
+//     kernels keep 3 or 5 stages and counted waits).  Pieces outside the matrix / the conv input are fetched from a
+//     16-byte zero block.
 //   * 128x128 or 64x64 output tile per 4-wave workgroup (2x2 waves, 4x4 / 2x2 MFMA 16x16x32 fragments per wave),
 //     BK = 64, optional split-K (fp32 partials + splitk_reduce_kernel) and the fused A-row-sum of the wgrad GEMMs.
 #include <cstring>
 #include "gemm_common.h"
+#include "lds_dma.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-__device__ __attribute__((aligned(16))) uint4 g_zero16 = {0u, 0u, 0u, 0u};
-
 // operand kinds (compile-time: the K loop has no mode branches): layout x addressing
-enum { G_KC_DENSE = 0, G_KC_CONV1D = 1, G_KC_CONV2D = 2, G_RC_DENSE = 3, G_RC_CONV1D = 4, G_RC_CONV2D = 5, G_KC_TCONV2D = 6,
+// (the values are part of the kernel symbols; 3..5 were the register-transposed kinds of the row-contiguous operands)
+enum { G_KC_DENSE = 0, G_KC_CONV1D = 1, G_KC_CONV2D = 2, G_KC_TCONV2D = 6,
        G_TR_DENSE = 7, G_TR_CONV1D = 8, G_TR_CONV2D = 9 };   // row-contiguous operands, LDS-DMA staged + transpose reads
 #define S2S_IS_TR(KIND) ((KIND) >= G_TR_DENSE)
-
-// LDS image of an operand tile with BKT bf16 per row (16-byte pieces): piece c of row r lives at
-//   BKT = 64 (128-B rows, 8 pieces): r*128 + ((c ^ ((r>>1)&7)) << 4)
-//   BKT = 32 ( 64-B rows, 4 pieces): r*64  + ((c ^ ((-(r>>2))&3)) << 4)
-// both maps put the 16 lanes of every ds_read_b128 lane group (rows r..r+15 at pieces c / c^1) on 16 distinct
-// 16-byte bank slots of the 256-byte LDS row.
-template <int BKT> __device__ __forceinline__ int swz_of(int r) { return BKT == 64 ? ((r >> 1) & 7) : ((-(r >> 2)) & 3); }
-template <int BKT> __device__ __forceinline__ int lds_off_t(int r, int c) { return r * (BKT * 2) + ((c ^ swz_of<BKT>(r)) << 4); }
-__device__ __forceinline__ int lds_off(int r, int c) { return lds_off_t<64>(r, c); }
-
-// address of the zero block as an opaque per-lane value: keeps `ok ? src : zero` a plain 64-bit select, so ONE DMA /
-// load instruction serves valid and padding lanes alike (a visible global address makes hipcc split every load in two
-// EXEC-masked halves with a branch around each)
-__device__ __forceinline__ uint64_t zero_addr() {
-  uint64_t z = reinterpret_cast<uint64_t>(&g_zero16);
-  asm volatile("" : "+v"(z));
-  return z;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // K-contiguous operand: ROWS/32 LDS-DMA instructions per wave and K tile (64 lanes x 16 B = 8 rows each).
 // All address arithmetic is select-based (no branches around the DMA); conv taps advance by compare-and-wrap
 // from the tile's uniform (tap, channel) origin instead of a per-lane division (needs C >= 64).
 // ---------------------------------------------------------------------------------------------------------
-template <int ROWS, int KIND, int BKT = 64>
+template <int ROWS, int KIND>
 struct KcStage {
+  static constexpr int BKT = 64;                       // bf16 per row of the tile
   static constexpr int PIECES = BKT / 8;               // 16-byte pieces per row
   static constexpr int RPI = 64 / PIECES;              // rows per DMA instruction (64 lanes x 16 B)
   static constexpr int NI = ROWS / RPI / 4;            // DMA instructions per wave and tile
@@ -88,8 +69,8 @@ struct KcStage {
       scalar_ok = elems * 2 < (1ll << 32) && o.C % BKT == 0;
     }
     // rows of group g = 4i + wave: rl = g*RPI + lane/PIECES ; the swizzle term of rl does not depend on i
-    // (BKT 64: ((g&1)*4 + (lane>>4)) & 7 with g&1 == wave&1 ; BKT 32: (-(lane>>4)) & 3)
-    piece8 = ((lane % PIECES) ^ swz_of<BKT>(wave * RPI + lane / PIECES)) << 3;
+    // (((g&1)*4 + (lane>>4)) & 7 with g&1 == wave&1)
+    piece8 = ((lane % PIECES) ^ lds_swz(wave * RPI + lane / PIECES)) << 3;
     // row index -> image position by multiply-high (exact: the host checked rows * extent < 2^32, rows_fit_fastdiv)
     const fastdiv_t fd0 = fastdiv_make(KIND == G_KC_TCONV2D ? o.T1 * o.F1 : (KIND == G_KC_CONV2D ? o.F2 : 1));
     const fastdiv_t fd1 = fastdiv_make(KIND == G_KC_TCONV2D ? o.F1 : (KIND == G_KC_CONV2D ? o.T2 : 1));
@@ -219,95 +200,6 @@ struct KcStage {
 };
 
 // ---------------------------------------------------------------------------------------------------------
-// Row-contiguous operand: 8x8 register-block transpose (one block per thread; ROWS blocks per tile)
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t perm_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-__device__ __forceinline__ uint32_t perm_hi(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-
-template <int ROWS, int KIND>
-struct RcStage {
-  // The tile is ROWS/8 row blocks x 8 k blocks of 8x8 elements.  All 256 threads take part: TPB threads share a
-  // block, each loading KS = 8/TPB consecutive k (16 B = 8 rows per load) and writing, per row, its KS k-values
-  // (8 or 4 bytes) into the row's 16-byte piece of the swizzled image.
-  // (Measured: for 128-row tiles one thread per block -- 8 loads, 8 ds_write_b128, half the threads idle -- is the
-  // faster arrangement, for 64-row tiles four threads per block.)
-  static constexpr int RB = ROWS / 8;
-  static constexpr int TPB = ROWS == 64 ? 4 : 1;
-  static constexpr int KS = 8 / TPB;         // k per thread
-  static constexpr int ACTIVE = ROWS * TPB;  // threads that carry a (partial) block
-  uint4 reg[KS];
-  __device__ __forceinline__ void load(const s2svc_operand& o, const bf16_t* base, int r0, int R, int k0, int K) {
-    if (ACTIVE < 256 && threadIdx.x >= ACTIVE) return;
-    const int rb = threadIdx.x % RB, rest = threadIdx.x / RB;
-    const int kb = rest / TPB, sub = rest % TPB;
-    const int r = r0 + rb * 8;
-    int tap = 0, c = r;
-    if (KIND != G_RC_DENSE) { tap = r / o.C; c = r - tap * o.C; }
-    const uint64_t zaddr = zero_addr();
-    // the KS consecutive k of a thread walk (b, t2, f2) / (b, t) incrementally: one division per tile, not per load
-    const int kfirst = k0 + kb * 8 + sub * KS;
-    int f2 = 0, t2 = 0, bb = 0, t = 0;
-    if (KIND == G_RC_CONV2D) {
-      const int bt = kfirst / o.F2;
-      f2 = kfirst - bt * o.F2;
-      bb = bt / o.T2;
-      t2 = bt - bb * o.T2;
-    } else if (KIND == G_RC_CONV1D) {
-      t = kfirst % o.T;
-    }
-    const int kh = tap / 3, kw = tap - kh * 3;
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-      const int k = kfirst + j;
-      bool ok = r < R && k < K;
-      int64_t off;
-      if (KIND == G_RC_DENSE) {
-        off = (int64_t)k * o.ld + r;
-      } else if (KIND == G_RC_CONV1D) {
-        const int tt = t + tap - o.pad;
-        ok = ok && tt >= 0 && tt < o.T;
-        off = (int64_t)(k + tap - o.pad) * o.ld + c;
-        if (++t == o.T) t = 0;
-      } else {
-        off = ((int64_t)(bb * o.T1 + 2 * t2 + kh) * o.F1 + (2 * f2 + kw)) * o.ld + c;
-        if (++f2 == o.F2) { f2 = 0; if (++t2 == o.T2) { t2 = 0; ++bb; } }
-      }
-      reg[j] = *reinterpret_cast<const uint4*>(ok ? reinterpret_cast<uint64_t>(base + off) : zaddr);
-    }
-  }
-  __device__ __forceinline__ void store(char* lds) const {
-    if (ACTIVE < 256 && threadIdx.x >= ACTIVE) return;
-    const int rb = threadIdx.x % RB, rest = threadIdx.x / RB;
-    const int kb = rest / TPB, sub = rest % TPB;
-    // element e (row rb*8+e) of reg[j] sits in dword e/2, half e%2
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      char* dst = lds + lds_off(rb * 8 + e, kb) + sub * (KS * 2);
-      if (KS == 8) {
-        uint32_t a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = (&reg[j % KS].x)[e >> 1];
-        uint4 v;
-        v.x = (e & 1) ? perm_hi(a[0], a[1]) : perm_lo(a[0], a[1]);
-        v.y = (e & 1) ? perm_hi(a[2], a[3]) : perm_lo(a[2], a[3]);
-        v.z = (e & 1) ? perm_hi(a[4], a[5]) : perm_lo(a[4], a[5]);
-        v.w = (e & 1) ? perm_hi(a[6], a[7]) : perm_lo(a[6], a[7]);
-        *reinterpret_cast<uint4*>(dst) = v;
-      } else if (KS == 4) {
-        const uint32_t a0 = (&reg[0].x)[e >> 1], a1 = (&reg[1 % KS].x)[e >> 1], a2 = (&reg[2 % KS].x)[e >> 1], a3 = (&reg[3 % KS].x)[e >> 1];
-        uint2 v;
-        v.x = (e & 1) ? perm_hi(a0, a1) : perm_lo(a0, a1);
-        v.y = (e & 1) ? perm_hi(a2, a3) : perm_lo(a2, a3);
-        *reinterpret_cast<uint2*>(dst) = v;
-      } else {
-        const uint32_t a0 = (&reg[0].x)[e >> 1], a1 = (&reg[1 % KS].x)[e >> 1];
-        *reinterpret_cast<uint32_t*>(dst) = (e & 1) ? perm_hi(a0, a1) : perm_lo(a0, a1);
-      }
-    }
-  }
-};
-
-// ---------------------------------------------------------------------------------------------------------
 // Row-contiguous operand WITHOUT the register transposes: the tile is DMA-ed k-major into LDS and the MFMA fragments
 // are read with ds_read_b64_tr_b16 (gfx950's transposing LDS read: a 16-lane group reads a [4 k][16 rows] block, lane
 // c of the group receives the 4 k-values of row c).  LDS image of a BK = 64 tile: 2 k-halves x ROWS/16 subtiles of
@@ -317,9 +209,6 @@ struct RcStage {
 // k-half -- a PERMUTATION of the MFMA's k positions, harmless because both operands of the product use it
 // (a K-contiguous partner reads the same positions: kc_fragment_perm).
 // ---------------------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(4))) short s16x4_t;
-typedef __attribute__((address_space(3))) s16x4_t lds_s16x4_t;
-
 template <int ROWS, int KIND>
 struct TrStage {
   static constexpr int SUB = ROWS / 16;             // subtiles per k-half
@@ -438,60 +327,39 @@ struct TrStage {
 // fragment of a K-contiguous (swizzled-piece) tile whose PARTNER is TR-staged: the same k positions as tr_fragment,
 // k = 4g..4g+3 and 16+4g..16+4g+3 of the k-half = half a 16-byte piece each (two ds_read_b64)
 __device__ __forceinline__ bf16x8_t kc_fragment_perm(const char* stage, int row, int ks, int g) {
-  typedef __attribute__((ext_vector_type(4))) short s16x4;
-  typedef __attribute__((ext_vector_type(8))) short s16x8;
-  const s16x4 lo = *reinterpret_cast<const s16x4*>(stage + lds_off(row, ks * 4 + (g >> 1)) + (g & 1) * 8);
-  const s16x4 hi = *reinterpret_cast<const s16x4*>(stage + lds_off(row, ks * 4 + 2 + (g >> 1)) + (g & 1) * 8);
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  const s16x4_t lo = *reinterpret_cast<const s16x4_t*>(stage + lds_off(row, ks * 4 + (g >> 1)) + (g & 1) * 8);
+  const s16x4_t hi = *reinterpret_cast<const s16x4_t*>(stage + lds_off(row, ks * 4 + 2 + (g >> 1)) + (g & 1) * 8);
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8_t, v);
 }
 
 // MFMA fragment of row block `mt` (16 rows), k-half `ks` of a TR-staged tile
 template <int ROWS>
 __device__ __forceinline__ bf16x8_t tr_fragment(const char* stage, int mt, int ks, int lane) {
-  const char* p = stage + (ks * (ROWS / 16) + mt) * 1024 + ((lane >> 4) * 4 + ((lane & 15) >> 2)) * 32 + (lane & 3) * 8;
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)p);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_t*)(p + 512));
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
+  return tr_fragment_read(stage + (ks * (ROWS / 16) + mt) * 1024, 0, lane);
 }
 
-// XCD-aware tile order.  The dispatcher deals consecutive workgroup ids round-robin to the 8 XCDs (each with its own
-// L2); handing XCD x the x-th CONTIGUOUS run of output tiles (row-major, n fastest) makes the workgroups that run
-// side by side on one XCD share A row panels and B column panels through that L2 instead of each pulling them over
-// the fabric.  Bijective for any grid size; z-planes (batch / split-K) keep the plain order unless the plane is a
-// multiple of 8 workgroups (the XCD phase of a plane would otherwise depend on z).
+// XCD-aware tile order (xcd_contiguous_id over the row-major tiles, n fastest); z-planes (batch / split-K) keep the plain order
+// unless the plane is a multiple of 8 workgroups (the XCD phase of a plane would otherwise depend on z).
 __device__ __forceinline__ void tile_of_block(int& bm, int& bn) {
   const int gx = gridDim.x, nwg = gridDim.x * gridDim.y;
   int id = blockIdx.y * gx + blockIdx.x;
-  if (gridDim.z == 1 || (nwg & 7) == 0) {
-    const int q = nwg >> 3, r = nwg & 7;
-    const int xcd = id & 7, j = id >> 3;
-    id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-  }
+  if (gridDim.z == 1 || (nwg & 7) == 0) id = xcd_contiguous_id(id, nwg);
   bm = id / gx;
   bn = id - bm * gx;
 }
 
-template <int ROWS, int KIND, int CLS = (S2S_IS_TR(KIND) ? 2 : ((KIND >= G_RC_DENSE && KIND <= G_RC_CONV2D) ? 1 : 0))> struct Stage;
-template <int ROWS, int KIND> struct Stage<ROWS, KIND, 2> {
+// the staging of one operand by its kind: K-contiguous (swizzled pieces) or row-contiguous (k-major, transpose reads)
+template <int ROWS, int KIND, bool TR = S2S_IS_TR(KIND)> struct Stage;
+template <int ROWS, int KIND> struct Stage<ROWS, KIND, true> {
   TrStage<ROWS, KIND> s;
   __device__ __forceinline__ void init(const s2svc_operand& o, int r0, int R) { s.init(o, r0, R); }
   __device__ __forceinline__ void issue(const s2svc_operand& o, const bf16_t* base, int r0, int R, int k0, int K, char* lds) { s.issue(o, base, r0, R, k0, K, lds); }
-  __device__ __forceinline__ void finish(char*) const {}
 };
-template <int ROWS, int KIND> struct Stage<ROWS, KIND, 0> {
+template <int ROWS, int KIND> struct Stage<ROWS, KIND, false> {
   KcStage<ROWS, KIND> s;
   __device__ __forceinline__ void init(const s2svc_operand& o, int r0, int R) { s.init(o, r0, R); }
   __device__ __forceinline__ void issue(const s2svc_operand& o, const bf16_t* base, int, int, int k0, int K, char* lds) { s.issue(o, base, k0, K, lds); }
-  __device__ __forceinline__ void finish(char*) const {}
-};
-template <int ROWS, int KIND> struct Stage<ROWS, KIND, 1> {
-  RcStage<ROWS, KIND> s;
-  __device__ __forceinline__ void init(const s2svc_operand&, int, int) {}
-  __device__ __forceinline__ void issue(const s2svc_operand& o, const bf16_t* base, int r0, int R, int k0, int K, char*) { s.load(o, base, r0, R, k0, K); }
-  __device__ __forceinline__ void finish(char* lds) const { s.store(lds); }
 };
 
 // One output tile of one GEMM: the body shared by the plain launch (one problem per grid) and the grouped launch (several
@@ -528,8 +396,6 @@ __device__ __forceinline__ void gemm_glds_tile(const s2svc_gemm_desc& d, int til
   if (kt_begin < kt_end) {
     sa.issue(d.A, Ab, m0, d.M, kt_begin * BK, d.K, smem);
     sb.issue(d.B, Bb, n0, d.N, kt_begin * BK, d.K, smem + ABYTES);
-    sa.finish(smem);
-    sb.finish(smem + ABYTES);
   }
   __syncthreads();                 // (drains the DMA: the compiler places vmcnt(0) ahead of the barrier)
 
@@ -582,10 +448,6 @@ __device__ __forceinline__ void gemm_glds_tile(const s2svc_gemm_desc& d, int til
 #pragma unroll
         for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
     }
-    if (more) {
-      sa.finish(An);
-      sb.finish(An + ABYTES);
-    }
     __syncthreads();
   }
 
@@ -614,25 +476,15 @@ __global__ __launch_bounds__(256) void gemm_glds_kernel(const s2svc_gemm_desc d)
   gemm_glds_tile<BM, BN, AMODE, BMODE>(d, tile_m, tile_n, zb, zs, smem);
 }
 
-// Grouped launch: up to S2S_GROUP_MAX independent GEMMs (the weight-gradient GEMMs of a few consecutive layers, queued
-// during backward) as ONE grid.  tile_start[p] .. tile_start[p+1] are the workgroups of problem p (row-major tiles).
-// The descriptors travel BY VALUE in the kernel-argument segment (nothing to upload; hipGraph capture records them with
-// the node).  Each workgroup runs the full K loop of its tile: with several problems' tiles in flight the grid fills
+// Grouped launch (group_args, lds_dma.h): the weight-gradient GEMMs of a few consecutive layers, queued during backward, as ONE
+// grid of row-major tiles.  Each workgroup runs the full K loop of its tile: with several problems' tiles in flight the grid fills
 // the chip without split-K, so there is no partial-sum workspace and no reduction pass.
-#define S2S_GROUP_MAX 10                                   /* 10 * 384 B + prefix sums < the 4 KB kernarg limit */
-struct group_args {
-  s2svc_gemm_desc d[S2S_GROUP_MAX];
-  int32_t tile_start[S2S_GROUP_MAX + 1];
-  int32_t n;
-};
-static_assert(sizeof(group_args) <= 4096, "kernel arguments are limited to 4 KB");
-
 template <int BM, int BN, int AMODE, int BMODE>
 __global__ __launch_bounds__(256) void gemm_grouped_kernel(const group_args g) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * (BM + BN) * 128];
   int p = 0;                                              // tile_start[p] <= blockIdx.x < tile_start[p + 1]
 #pragma unroll
-  for (int i = 1; i < S2S_GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
+  for (int i = 1; i < GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
   const s2svc_gemm_desc& d = g.d[p];
   const int t = (int)blockIdx.x - g.tile_start[p];
   const int tiles_n = (d.N + BN - 1) / BN;
@@ -648,9 +500,9 @@ __global__ __launch_bounds__(256) void gemm_grouped_kernel(const group_args g) {
 template <int BM, int BN, int AMODE, int BMODE>
 __global__ __launch_bounds__(256) void gemm_grouped_batched_kernel(const group_args g) {
   __shared__ __attribute__((aligned(1024))) char smem[2 * (BM + BN) * 128];
-  int p = 0;
+  int p = 0;                                              // tile_start[p] <= blockIdx.x < tile_start[p + 1]
 #pragma unroll
-  for (int i = 1; i < S2S_GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
+  for (int i = 1; i < GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= (int)blockIdx.x) ? 1 : 0;
   const s2svc_gemm_desc& d = g.d[p];
   const int t = (int)blockIdx.x - g.tile_start[p];
   const int tiles_n = (d.N + BN - 1) / BN;
@@ -661,27 +513,6 @@ __global__ __launch_bounds__(256) void gemm_grouped_batched_kernel(const group_a
   gemm_glds_tile<BM, BN, AMODE, BMODE>(d, tile_m, r - tile_m * tiles_n, zb, 0, smem);
 }
 
-// The same with a CAPPED grid: gridDim.x workgroups walk all tiles.  Weight-gradient launches run on side
-// streams beside the data-gradient chain; one workgroup per tile (500-1300 of them) takes every CU slot for the length of the
-// launch and the chain's small kernels queue behind them, a capped grid leaves slots free.  Same tile code: same bits.
-template <int BM, int BN, int AMODE, int BMODE>
-__global__ __launch_bounds__(256) void gemm_grouped_capped_kernel(const group_args g) {
-  __shared__ __attribute__((aligned(1024))) char smem[2 * (BM + BN) * 128];
-  const int total = g.tile_start[S2S_GROUP_MAX];
-#pragma unroll 1
-  for (int bt = (int)blockIdx.x; bt < total; bt += (int)gridDim.x) {
-    int p = 0;
-#pragma unroll
-    for (int i = 1; i < S2S_GROUP_MAX; ++i) p += (i < g.n && g.tile_start[i] <= bt) ? 1 : 0;
-    const s2svc_gemm_desc& d = g.d[p];
-    const int t = bt - g.tile_start[p];
-    const int tiles_n = (d.N + BN - 1) / BN;
-    const int tile_m = t / tiles_n;
-    gemm_glds_tile<BM, BN, AMODE, BMODE>(d, tile_m, t - tile_m * tiles_n, 0, 0, smem);
-    __syncthreads();
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------------
 // All-DMA variant (both operands K-contiguous): NS LDS stages, NS-1 tiles in flight.  The wait for tile t is a
 // COUNTED s_waitcnt (the DMAs of the later tiles stay in flight across the barrier) followed by a raw s_barrier;
@@ -689,13 +520,12 @@ __global__ __launch_bounds__(256) void gemm_grouped_capped_kernel(const group_ar
 // Every wave issues exactly NI_A + NI_B DMA instructions per tile, so "tile t landed" == vmcnt <= (tiles issued
 // after t) * (NI_A + NI_B).
 // ---------------------------------------------------------------------------------------------------------
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-template <int BM, int BN, int KA, int KB, int NS, int BK, bool LEAN = false>
+template <int BM, int BN, int KA, int KB, int NS, bool LEAN = false>
 __global__ __launch_bounds__(256) void gemm_dma_kernel(const s2svc_gemm_desc d) {
+  constexpr int BK = 64;
   constexpr int FM = BM / 32, FN = BN / 32;
   constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2, STAGE_BYTES = ABYTES + BBYTES;
-  constexpr int PER_TILE = KcStage<BM, KA, BK>::NI + KcStage<BN, KB, BK>::NI;   // DMA instructions per wave and tile
+  constexpr int PER_TILE = KcStage<BM, KA>::NI + KcStage<BN, KB>::NI;   // DMA instructions per wave and tile
   __shared__ __attribute__((aligned(1024))) char smem[NS * STAGE_BYTES];
 
   const int splitk = d.splitk > 1 ? d.splitk : 1;
@@ -720,8 +550,8 @@ __global__ __launch_bounds__(256) void gemm_dma_kernel(const s2svc_gemm_desc d) 
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  KcStage<BM, KA, BK> sa;
-  KcStage<BN, KB, BK> sb;
+  KcStage<BM, KA> sa;
+  KcStage<BN, KB> sb;
   sa.init(d.A, m0, d.M);
   sb.init(d.B, n0, d.N);
   // prologue: NS-1 tiles in flight (tiles past the end are issued too -- they read the zero block -- so that the
@@ -748,9 +578,9 @@ __global__ __launch_bounds__(256) void gemm_dma_kernel(const s2svc_gemm_desc d) 
     for (int ks = 0; ks < BK / 32; ++ks) {
       bf16x8_t a[FM], b[FN];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(As + lds_off_t<BK>(wm + i * 16 + lr, ks * 4 + lg));
+      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(As + lds_off(wm + i * 16 + lr, ks * 4 + lg));
 #pragma unroll
-      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(Bs + lds_off_t<BK>(wn + j * 16 + lr, ks * 4 + lg));
+      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(Bs + lds_off(wn + j * 16 + lr, ks * 4 + lg));
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -787,7 +617,7 @@ __global__ __launch_bounds__(512) void gemm_dma_k2_kernel(const s2svc_gemm_desc 
   constexpr int BK = 64;
   constexpr int FM = BM / 32, FN = BN / 32;
   constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2, STAGE_BYTES = ABYTES + BBYTES, RING = NS * STAGE_BYTES;
-  constexpr int PER_TILE = KcStage<BM, G_KC_DENSE, BK>::NI + KcStage<BN, G_KC_DENSE, BK>::NI;
+  constexpr int PER_TILE = KcStage<BM, G_KC_DENSE>::NI + KcStage<BN, G_KC_DENSE>::NI;
   __shared__ __attribute__((aligned(1024))) char smem[2 * RING];
   static_assert(2 * RING >= 2 * BM * BN * 4, "the rings double as the partial-sum buffer and the fp32 C tiles");
   int tile_m, tile_n;
@@ -811,8 +641,8 @@ __global__ __launch_bounds__(512) void gemm_dma_k2_kernel(const s2svc_gemm_desc 
 #pragma unroll
     for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  KcStage<BM, G_KC_DENSE, BK> sa;
-  KcStage<BN, G_KC_DENSE, BK> sb;
+  KcStage<BM, G_KC_DENSE> sa;
+  KcStage<BN, G_KC_DENSE> sb;
   sa.init(d.A, m0, d.M);
   sb.init(d.B, n0, d.N);
 #pragma unroll
@@ -838,9 +668,9 @@ __global__ __launch_bounds__(512) void gemm_dma_k2_kernel(const s2svc_gemm_desc 
     for (int ks = 0; ks < BK / 32; ++ks) {
       bf16x8_t a[FM], b[FN];
 #pragma unroll
-      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(As + lds_off_t<BK>(wm + i * 16 + lr, ks * 4 + lg));
+      for (int i = 0; i < FM; ++i) a[i] = *reinterpret_cast<const bf16x8_t*>(As + lds_off(wm + i * 16 + lr, ks * 4 + lg));
 #pragma unroll
-      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(Bs + lds_off_t<BK>(wn + j * 16 + lr, ks * 4 + lg));
+      for (int j = 0; j < FN; ++j) b[j] = *reinterpret_cast<const bf16x8_t*>(Bs + lds_off(wn + j * 16 + lr, ks * 4 + lg));
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
@@ -874,34 +704,21 @@ __global__ __launch_bounds__(512) void gemm_dma_k2_kernel(const s2svc_gemm_desc 
   epilogue_flush_common<BM / 2, BN / 2>(d, m0 + wm, n0 + wn, cs);
 }
 
-constexpr bool k2_enabled() { return true; }      // long reductions over few tiles: the 8-wave split-K kernel
-constexpr int k2_min_tiles() { return 12; }       // K tiles from which the split is taken
+constexpr int k2_min_tiles() { return 12; }       // K tiles from which the 8-wave split-K kernel (long reductions over few tiles) is taken
 
-constexpr bool lean_enabled() { return true; }    // launches with the common epilogue carry the lean flush code
+constexpr int deep_min_tiles() { return 16; }     // K tiles from which the 5-stage variant of the 32x64 kernel is taken
 
-constexpr int dma_stages() { return 0; }          // 0 = the built-in stage policy, see launch_kinds
-
-constexpr bool deep_stages() { return true; }     // the 5-stage variant of the 32x64 kernel for long reductions
-
-constexpr int deep_min_tiles() { return 16; }     // K tiles from which the 5-stage variant is taken
-
-constexpr bool tr_enabled() { return true; }      // row-contiguous operands through ds_read_b64_tr_b16
-
+// row-contiguous operands take the transpose-read kinds: k-major LDS-DMA staging + ds_read_b64_tr_b16
 int kind_of(const s2svc_operand& o) {
   if (o.mode == S2SVC_OP_TCONV2D_S2) return o.layout == S2SVC_LAYOUT_KC ? G_KC_TCONV2D : -1;
-  const int base = o.layout == S2SVC_LAYOUT_RC ? G_RC_DENSE : G_KC_DENSE;
+  const int base = o.layout == S2SVC_LAYOUT_RC ? G_TR_DENSE : G_KC_DENSE;
   return base + (o.mode == S2SVC_OP_DENSE ? 0 : (o.mode == S2SVC_OP_CONV1D ? 1 : 2));
 }
 
 // the operand-kind pairs the autograd code issues (ops/functional.py); anything else stays on the older kernels
 template <int BM, int BN>
 bool launch_kinds(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
-  int ka = kind_of(d.A), kb = kind_of(d.B);
-  // row-contiguous operands: k-major LDS-DMA staging + transpose reads
-  if (tr_enabled()) {
-    if (ka >= G_RC_DENSE && ka <= G_RC_CONV2D) ka += G_TR_DENSE - G_RC_DENSE;
-    if (kb >= G_RC_DENSE && kb <= G_RC_CONV2D) kb += G_TR_DENSE - G_RC_DENSE;
-  }
+  const int ka = kind_of(d.A), kb = kind_of(d.B);
 #define S2S_GLDS_CASE(KA, KB)                                                                       \
   if (ka == KA && kb == KB) {                                                                      \
     s2s_gemm_route(BM == 128 ? "glds<128,128," #KA "," #KB ">" : "glds<64,64," #KA "," #KB ">");     \
@@ -912,14 +729,15 @@ bool launch_kinds(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   // 128x128 tile keeps two stages (64 KB, 2 workgroups per CU -- a third stage leaves one workgroup per CU and
   // measured ~2x slower; BK = 32 with 3-4 stages measured 10-15 % slower).
 #define S2S_DMA_CASE(KA, KB)                                                                        \
-  if (ka == KA && kb == KB && !d.a_rowsum && BM == 64 && dma_stages() != 2) {                      \
+  if (ka == KA && kb == KB && !d.a_rowsum && BM == 64) {                                           \
     s2s_gemm_route("glds_dma<64,64," #KA "," #KB ",3>");                                           \
-    hipLaunchKernelGGL((gemm_dma_kernel<64, 64, KA, KB, 3, 64>), grid, dim3(256), 0, st, d);       \
+    hipLaunchKernelGGL((gemm_dma_kernel<64, 64, KA, KB, 3>), grid, dim3(256), 0, st, d);           \
     return true;                                                                                   \
   }
-  if (ka == G_KC_DENSE && kb == G_KC_DENSE && !d.a_rowsum && BM == 64 && dma_stages() != 2 && lean_enabled() && epilogue_common_ok(d)) {
+  // (launches with the common epilogue carry the lean flush code)
+  if (ka == G_KC_DENSE && kb == G_KC_DENSE && !d.a_rowsum && BM == 64 && epilogue_common_ok(d)) {
     s2s_gemm_route("glds_dma<64,64,G_KC_DENSE,G_KC_DENSE,3,lean>");
-    hipLaunchKernelGGL((gemm_dma_kernel<64, 64, G_KC_DENSE, G_KC_DENSE, 3, 64, true>), grid, dim3(256), 0, st, d);
+    hipLaunchKernelGGL((gemm_dma_kernel<64, 64, G_KC_DENSE, G_KC_DENSE, 3, true>), grid, dim3(256), 0, st, d);
     return true;
   }
   S2S_DMA_CASE(G_KC_DENSE, G_KC_DENSE)
@@ -928,16 +746,18 @@ bool launch_kinds(const s2svc_gemm_desc& d, dim3 grid, hipStream_t st) {
   S2S_DMA_CASE(G_KC_TCONV2D, G_KC_DENSE)
 #undef S2S_DMA_CASE
   S2S_GLDS_CASE(G_KC_DENSE, G_KC_DENSE)      // linear forward, attention scores
-  S2S_GLDS_CASE(G_KC_DENSE, G_RC_DENSE)      // linear dgrad, P.V
-  S2S_GLDS_CASE(G_RC_DENSE, G_RC_DENSE)      // linear wgrad
-  S2S_GLDS_CASE(G_RC_DENSE, G_KC_DENSE)
   S2S_GLDS_CASE(G_KC_CONV1D, G_KC_DENSE)     // Conv1d forward (implicit im2col)
-  S2S_GLDS_CASE(G_KC_CONV1D, G_RC_DENSE)     // Conv1d dgrad
-  S2S_GLDS_CASE(G_RC_DENSE, G_RC_CONV1D)     // Conv1d wgrad
   S2S_GLDS_CASE(G_KC_CONV2D, G_KC_DENSE)     // Conv2d 3x3 s2 forward
-  S2S_GLDS_CASE(G_RC_DENSE, G_RC_CONV2D)     // Conv2d wgrad
-  S2S_GLDS_CASE(G_KC_TCONV2D, G_KC_DENSE)    // Conv2d dgrad, one parity class (transposed convolution, c_map store)
-  S2S_GLDS_CASE(G_TR_DENSE, G_TR_DENSE)      // linear wgrad, transpose-read path
+  // Conv2d dgrad, one parity class (transposed convolution, c_map store).  128x128 only: the DMA case above takes every
+  // 64x64 descriptor (s2svc_gemm refuses a_rowsum with a transposed-convolution operand).
+  if constexpr (BM == 128) {
+    if (ka == G_KC_TCONV2D && kb == G_KC_DENSE) {
+      s2s_gemm_route("glds<128,128,G_KC_TCONV2D,G_KC_DENSE>");
+      hipLaunchKernelGGL((gemm_glds_kernel<128, 128, G_KC_TCONV2D, G_KC_DENSE>), grid, dim3(256), 0, st, d);
+      return true;
+    }
+  }
+  S2S_GLDS_CASE(G_TR_DENSE, G_TR_DENSE)      // linear wgrad
   S2S_GLDS_CASE(G_KC_DENSE, G_TR_DENSE)      // linear dgrad (no transposed weight copy), P.V
   S2S_GLDS_CASE(G_TR_DENSE, G_KC_DENSE)
   S2S_GLDS_CASE(G_KC_CONV1D, G_TR_DENSE)     // Conv1d dgrad
@@ -955,10 +775,6 @@ bool operand_ok(const s2svc_operand& o) {
 }
 
 constexpr int big_min_tiles() { return 192; }     // 128x128 tiles from this many of them on
-
-constexpr bool bm32_enabled() { return true; }
-
-constexpr bool disabled() { return false; }
 
 // the kernels split row indices into image positions with multiply-high divisions, exact while rows * extent < 2^32
 bool rows_fit_fastdiv(const s2svc_gemm_desc& d) {
@@ -1053,8 +869,8 @@ extern "C" int s2svc_tconv2d_weights(int O, int C, const float* w, void* out_bf1
 // ---- grouped weight-gradient GEMMs (C[N_out, N_in] (+)= dY^T . X, both operands row-contiguous) -------------------
 extern "C" int s2svc_gemm_grouped_ok(const s2svc_gemm_desc* desc) {
   const s2svc_gemm_desc& d = *desc;
-  if (disabled() || d.dtype != S2S_BF16 || d.nb0 * d.nb1 != 1) return 0;
-  if (kind_of(d.A) != G_RC_DENSE || kind_of(d.B) != G_RC_DENSE) return 0;
+  if (d.dtype != S2S_BF16 || d.nb0 * d.nb1 != 1) return 0;
+  if (kind_of(d.A) != G_TR_DENSE || kind_of(d.B) != G_TR_DENSE) return 0;
   if (!operand_ok(d.A) || !operand_ok(d.B) || !extent_ok(d.A, d.M) || !extent_ok(d.B, d.N)) return 0;
   if (d.emask || d.drop_p > 0.f || d.M <= 0 || d.N <= 0 || d.K <= 0) return 0;
   return 1;
@@ -1063,7 +879,7 @@ extern "C" int s2svc_gemm_grouped_ok(const s2svc_gemm_desc* desc) {
 // the parity-class GEMMs of one transposed convolution (Conv2d data gradient) may share a launch as well: same operand
 // kinds, disjoint output pixels (c_map), reductions of 1 / 2 / 2 / 4 taps -- one grid instead of four short ones
 static bool tconv_group_ok(const s2svc_gemm_desc& d) {
-  if (disabled() || d.dtype != S2S_BF16 || d.nb0 * d.nb1 != 1 || !d.c_map) return false;
+  if (d.dtype != S2S_BF16 || d.nb0 * d.nb1 != 1 || !d.c_map) return false;
   if (kind_of(d.A) != G_KC_TCONV2D || kind_of(d.B) != G_KC_DENSE) return false;
   if (!operand_ok(d.A) || !operand_ok(d.B) || !extent_ok(d.A, d.K) || !extent_ok(d.B, d.K) || !rows_fit_fastdiv(d)) return false;
   if (d.emask || d.drop_p > 0.f || d.a_rowsum || d.M <= 0 || d.N <= 0 || d.K <= 0) return false;
@@ -1076,7 +892,7 @@ extern "C" int s2svc_gemm_grouped(const s2svc_gemm_desc* descs, int n, int tile,
   S2S_REQUIRE(descs && n > 0 && (tile == 64 || tile == 128), "gemm_grouped: bad args");
   hipStream_t st = (hipStream_t)stream;
   if (tconv_group_ok(descs[0])) {
-    S2S_REQUIRE(tile == 128 && n <= S2S_GROUP_MAX, "gemm_grouped: transposed-convolution groups take 128x128 tiles, <= 10 problems");
+    S2S_REQUIRE(tile == 128 && n <= GROUP_MAX, "gemm_grouped: transposed-convolution groups take 128x128 tiles, <= 10 problems");
     group_args g;
     std::memset(&g, 0, sizeof(g));
     g.n = n;
@@ -1088,23 +904,20 @@ extern "C" int s2svc_gemm_grouped(const s2svc_gemm_desc* descs, int n, int tile,
       total += (int64_t)((descs[i].M + 127) / 128) * ((descs[i].N + 127) / 128);
       S2S_REQUIRE(total < (1ll << 30), "gemm_grouped: too many tiles");
     }
-    for (int i = n; i <= S2S_GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
+    for (int i = n; i <= GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
     hipLaunchKernelGGL((gemm_grouped_kernel<128, 128, G_KC_TCONV2D, G_KC_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
     S2S_CHECK_LAUNCH("gemm_grouped_kernel (tconv2d)");
     return 0;
   }
-  for (int i0 = 0; i0 < n; i0 += S2S_GROUP_MAX) {
-    const int cnt = (n - i0 < S2S_GROUP_MAX) ? n - i0 : S2S_GROUP_MAX;
+  for (int i0 = 0; i0 < n; i0 += GROUP_MAX) {
+    const int cnt = (n - i0 < GROUP_MAX) ? n - i0 : GROUP_MAX;
     for (int i = 0; i < cnt; ++i) {
       const s2svc_gemm_desc& d = descs[i0 + i];
       S2S_REQUIRE(s2svc_gemm_grouped_ok(&d), "gemm_grouped: a descriptor is not eligible (check s2svc_gemm_grouped_ok first)");
       S2S_REQUIRE(d.splitk <= 1, "gemm_grouped: grouped problems run unsplit (splitk must be <= 1)");
     }
-    int taken = 0;                                  // problems of exact 256 x 128 tiles: the 8-wave kernel (gemm_8ph.hip)
-    if (tr_enabled()) {
-      taken = s2svc_gemm_grouped_try_8ph(descs + i0, cnt, stream);
-      if (taken < 0) return taken;
-    }
+    const int taken = s2svc_gemm_grouped_try_8ph(descs + i0, cnt, stream);      // problems of exact 256 x 128 tiles: the 8-wave kernel (gemm_8ph.hip)
+    if (taken < 0) return taken;
     group_args g;
     std::memset(&g, 0, sizeof(g));
     int64_t total = 0;
@@ -1117,22 +930,11 @@ extern "C" int s2svc_gemm_grouped(const s2svc_gemm_desc* descs, int n, int tile,
       S2S_REQUIRE(total < (1ll << 30), "gemm_grouped: too many tiles");
     }
     if (g.n == 0) continue;
-    for (int i = g.n; i <= S2S_GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
-    static const int cap = 0;
-    if (tr_enabled() && cap > 0 && total > cap) {
-      if (tile == 128)
-        hipLaunchKernelGGL((gemm_grouped_capped_kernel<128, 128, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)cap), dim3(256), 0, st, g);
-      else
-        hipLaunchKernelGGL((gemm_grouped_capped_kernel<64, 64, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)cap), dim3(256), 0, st, g);
-    } else if (tr_enabled()) {
-      if (tile == 128)
-        hipLaunchKernelGGL((gemm_grouped_kernel<128, 128, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
-      else
-        hipLaunchKernelGGL((gemm_grouped_kernel<64, 64, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
-    } else if (tile == 128)
-      hipLaunchKernelGGL((gemm_grouped_kernel<128, 128, G_RC_DENSE, G_RC_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
+    for (int i = g.n; i <= GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
+    if (tile == 128)
+      hipLaunchKernelGGL((gemm_grouped_kernel<128, 128, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
     else
-      hipLaunchKernelGGL((gemm_grouped_kernel<64, 64, G_RC_DENSE, G_RC_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
+      hipLaunchKernelGGL((gemm_grouped_kernel<64, 64, G_TR_DENSE, G_TR_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
     S2S_CHECK_LAUNCH("gemm_grouped_kernel");
   }
   return 0;
@@ -1142,9 +944,9 @@ extern "C" int s2svc_gemm_grouped(const s2svc_gemm_desc* descs, int n, int tile,
 // eligible as a group (nothing was launched: the caller runs the problems one by one with s2svc_gemm), < 0 = error.
 extern "C" int s2svc_gemm_grouped_batched(const s2svc_gemm_desc* descs, int n, void* stream) {
   S2S_REQUIRE(descs && n > 0, "gemm_grouped_batched: bad args");
-  if (disabled() || !tr_enabled() || n > S2S_GROUP_MAX) return 1;
+  if (n > GROUP_MAX) return 1;
   const int ka = kind_of(descs[0].A), kb = kind_of(descs[0].B);
-  if (!((ka == G_KC_DENSE || ka == G_RC_DENSE) && kb == G_RC_DENSE)) return 1;
+  if (!((ka == G_KC_DENSE || ka == G_TR_DENSE) && kb == G_TR_DENSE)) return 1;
   group_args g;
   std::memset(&g, 0, sizeof(g));
   int64_t total128 = 0;
@@ -1157,8 +959,7 @@ extern "C" int s2svc_gemm_grouped_batched(const s2svc_gemm_desc* descs, int n, v
     total128 += (int64_t)((d.M + 127) / 128) * ((d.N + 127) / 128) * d.nb0 * d.nb1;
   }
   // 128 x 128 tiles once they fill the chip (the rule of the plain launch, over the group), else 64 x 64
-  static const int force_tile = 0;      // A/B aid
-  const int tile = force_tile == 64 || force_tile == 128 ? force_tile : (total128 >= 256 ? 128 : 64);
+  const int tile = total128 >= 256 ? 128 : 64;
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
     const s2svc_gemm_desc& d = descs[i];
@@ -1168,7 +969,7 @@ extern "C" int s2svc_gemm_grouped_batched(const s2svc_gemm_desc* descs, int n, v
     S2S_REQUIRE(total < (1ll << 30), "gemm_grouped_batched: too many tiles");
   }
   g.n = n;
-  for (int i = n; i <= S2S_GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
+  for (int i = n; i <= GROUP_MAX; ++i) g.tile_start[i] = (int32_t)total;
   hipStream_t st = (hipStream_t)stream;
   if (ka == G_KC_DENSE) {
     if (tile == 128) hipLaunchKernelGGL((gemm_grouped_batched_kernel<128, 128, G_KC_DENSE, G_TR_DENSE>), dim3((unsigned)total), dim3(256), 0, st, g);
@@ -1184,7 +985,7 @@ extern "C" int s2svc_gemm_grouped_batched(const s2svc_gemm_desc* descs, int n, v
 // returns 1 if launched here (the caller still runs the split-K reduction), 0 if the problem is not eligible
 extern "C" int s2svc_gemm_try_glds(const s2svc_gemm_desc* desc, void* stream) {
   const s2svc_gemm_desc& d = *desc;
-  if (disabled() || d.dtype != S2S_BF16) return 0;
+  if (d.dtype != S2S_BF16) return 0;
   if (kind_of(d.A) < 0 || kind_of(d.B) < 0 || kind_of(d.B) == G_KC_TCONV2D) return 0;
   if (!operand_ok(d.A) || !operand_ok(d.B)) return 0;
   if (!extent_ok(d.A, d.A.layout == S2SVC_LAYOUT_RC ? d.M : d.K)) return 0;
@@ -1205,29 +1006,28 @@ extern "C" int s2svc_gemm_try_glds(const s2svc_gemm_desc* desc, void* stream) {
   // other's load latency -- with one resident workgroup per CU the 6-step K loop of a 2016 x 384 x 384 linear is a
   // chain of exposed DMA latencies
   const int64_t tiles64 = (int64_t)((d.M + 63) / 64) * ((d.N + 63) / 64) * d.nb0 * d.nb1 * splitk;
-  if (!big && bm32_enabled() && tiles64 < 256 && d.M > 64 && !d.a_rowsum && kind_of(d.A) == G_KC_DENSE && kind_of(d.B) == G_KC_DENSE) {
+  if (!big && tiles64 < 256 && d.M > 64 && !d.a_rowsum && kind_of(d.A) == G_KC_DENSE && kind_of(d.B) == G_KC_DENSE) {
     dim3 grid((d.N + 63) / 64, (d.M + 31) / 32, d.nb0 * d.nb1 * splitk);
-    // long reductions (K >= 1024: the feed-forward / packed-projection data gradients of VTN, 18-24 K tiles) with few workgroups:
-    // five stages in flight (60 KB) instead of three -- with 2 tiles of lookahead (~0.7 us of MFMA work) every K tile waits for
-    // its own DMA round trip
-    const bool lean = lean_enabled() && epilogue_common_ok(d);
-    if (lean && k2_enabled() && splitk == 1 && d.nb0 * d.nb1 == 1 && (d.K + 63) / 64 >= k2_min_tiles()) {
+    const bool lean = epilogue_common_ok(d);            // (implies one problem, no split-K)
+    if (lean && (d.K + 63) / 64 >= k2_min_tiles()) {    // long reductions over few tiles: split K inside the workgroup
       s2s_gemm_route("glds_k2<32,64,3>");
       hipLaunchKernelGGL((gemm_dma_k2_kernel<32, 64, 3>), dim3(grid.x, grid.y, 1), dim3(512), 0, st, d);
       S2S_CHECK_LAUNCH("gemm_dma_k2_kernel");
       return 1;
     }
-    if (deep_stages() && (d.K + 63) / 64 / splitk >= deep_min_tiles()) {
-      s2s_gemm_route(lean ? "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5,lean>" : "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5>");
-      if (lean) hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 5, 64, true>), grid, dim3(256), 0, st, d);
-      else hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 5, 64>), grid, dim3(256), 0, st, d);
-    }
-    else if (lean) {
+    // long reductions (K >= 1024: the feed-forward / packed-projection data gradients of VTN, 18-24 K tiles) with few workgroups:
+    // five stages in flight (60 KB) instead of three -- with 2 tiles of lookahead (~0.7 us of MFMA work) every K tile waits for
+    // its own DMA round trip.  No lean variant: a lean launch this long took the split-K kernel above.
+    static_assert(deep_min_tiles() >= k2_min_tiles(), "the 5-stage kernel would need its lean variant");
+    if ((d.K + 63) / 64 / splitk >= deep_min_tiles()) {
+      s2s_gemm_route("glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5>");
+      hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 5>), grid, dim3(256), 0, st, d);
+    } else if (lean) {
       s2s_gemm_route("glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,3,lean>");
-      hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3, 64, true>), grid, dim3(256), 0, st, d);
+      hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3, true>), grid, dim3(256), 0, st, d);
     } else {
       s2s_gemm_route("glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,3>");
-      hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3, 64>), grid, dim3(256), 0, st, d);
+      hipLaunchKernelGGL((gemm_dma_kernel<32, 64, G_KC_DENSE, G_KC_DENSE, 3>), grid, dim3(256), 0, st, d);
     }
     S2S_CHECK_LAUNCH("gemm_dma_kernel");
     return 1;

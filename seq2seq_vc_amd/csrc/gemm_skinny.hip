@@ -104,8 +104,7 @@ template <typename T>
 void launch_skinny(const s2svc_gemm_desc& d, hipStream_t st) {
   dim3 grid((d.N + 15) / 16), block(256);
   const int mt = (d.M + 15) / 16;
-  static const bool lean_on = true;
-  if (lean_on && mt <= 2 && epilogue_lean_ok(d)) {
+  if (mt <= 2 && epilogue_lean_ok(d)) {
     if (mt == 1) { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,1,lean>" : "skinny<bf16,1,lean>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 1, true>), grid, block, 0, st, d); }
     else { s2s_gemm_route(sizeof(T) == 4 ? "skinny<f32,2,lean>" : "skinny<bf16,2,lean>"); hipLaunchKernelGGL((gemm_skinny_kernel<T, 2, true>), grid, block, 0, st, d); }
     return;

@@ -23,10 +23,8 @@
 // Dropout masks are functions of (seed, element index of the attention map), the same function the separate kernels use.
 // Roundings to bf16: qu and qv (stored, then read back as the operands of both score products), the stored map, and its dropped copy
 // bf16(stored map * keep).  Everything else is fp32.
-#include "common.h"
-#include "../../include/s2svc_hip.h"
+#include "lds_dma.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 namespace {
@@ -54,9 +52,6 @@ struct ra_fwd_args {
   bf16_t* qu; bf16_t* qv;       // (B, T, H * dk) contiguous
 };
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // LDS image of a 32-wide operand slice, as the LDS-DMA instruction writes it (lane-linear, 64-byte rows) with the XOR swizzle of
 // gemm_glds.hip applied to the per-lane SOURCE address and to the fragment read: piece c of row r lives at r*64 + ((c ^ swz(r)) << 4).
 __device__ __forceinline__ int swz32(int r) { return (-(r >> 2)) & 3; }

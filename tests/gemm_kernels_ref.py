@@ -655,23 +655,6 @@ _tables()
 CASES = [c for g in GROUPS.values() for c in g]
 MAX_MADDS = 0.6e9            # per case, for the float64 truth on the CPU (chosen, not measured)
 
-# Route names that no descriptor reaches on this build, each with the constexpr switch that decides it (csrc/gemm_glds.hip).
-_RC_KINDS = ("G_RC_DENSE", "G_RC_CONV1D", "G_RC_CONV2D")
-UNREACHABLE = {
-    "glds_dma<32,64,G_KC_DENSE,G_KC_DENSE,5,lean>":
-        "unreachable on this build: constexpr switch k2_enabled() is on -- a lean descriptor (one problem, no split-K) with >= deep_min_tiles() = 16 K "
-        "tiles has >= k2_min_tiles() = 12 of them and takes gemm_dma_k2_kernel first",
-    "glds<64,64,G_KC_TCONV2D,G_KC_DENSE>":
-        "unreachable on this build: constexpr switch dma_stages() is not 2, so the S2S_DMA_CASE in front of it takes every 64 x 64 descriptor without "
-        "a_rowsum, and s2svc_gemm refuses a_rowsum with a transposed-convolution operand",
-}
-for _bm in ("64,64", "128,128"):
-    for _ka, _kb in (("G_KC_DENSE", "G_RC_DENSE"), ("G_RC_DENSE", "G_RC_DENSE"), ("G_RC_DENSE", "G_KC_DENSE"), ("G_KC_CONV1D", "G_RC_DENSE"),
-                     ("G_RC_DENSE", "G_RC_CONV1D"), ("G_RC_DENSE", "G_RC_CONV2D")):
-        UNREACHABLE[f"glds<{_bm},{_ka},{_kb}>"] = ("unreachable on this build: constexpr switch tr_enabled() is on -- launch_kinds renames every row-contiguous "
-                                                  "operand kind to its transpose-read kind before the cases are tried")
-
-
 def routes_in_sources(csrc):
     """Every route name a launch site of csrc/gemm*.hip can hand to s2s_gemm_route / s2s_gemm_route_add: function-like macros that carry
     string literals are expanded at their invocations (`#P` stringifies), adjacent literals are joined, and each literal run inside a call of the
