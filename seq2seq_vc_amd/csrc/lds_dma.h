@@ -62,7 +62,7 @@ __device__ __forceinline__ int xcd_contiguous_id(int id, int nwg) {
 // The descriptors travel BY VALUE in the kernel-argument segment (nothing to upload; hipGraph capture records them with the node).
 // (The kernels find their problem with a loop of their own: behind a shared function the compiler schedules the nine compares
 // differently, and the grouped kernels are kept instruction for instruction.)
-constexpr int GROUP_MAX = 10;                              // 10 * 384 B + prefix sums < the 4 KB kernarg limit
+constexpr int GROUP_MAX = 10;                              // 10 * 392 B + 44 B of prefix sums + n = 3968 B < the 4 KB kernarg limit
 struct group_args {
   s2svc_gemm_desc d[GROUP_MAX];
   int32_t tile_start[GROUP_MAX + 1];

@@ -1,7 +1,6 @@
 """Host-side checks of AASVC.inference_batch (no GPU): the float64 restatements of tests/aasvc_batch_ref.py against stock torch and the
 reference's rule, the lengths of the two fixtures, the C ABI of the new launchers and the supported set of the fused inference core."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -9,9 +8,9 @@ import torch
 import torch.nn.functional as F
 
 import aasvc_batch_ref as AR
+import abi_header
 from seq2seq_vc_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("s2svc_convmod_infer", "s2svc_convmod_infer_supported", "s2svc_durations_finalize", "s2svc_interp_nearest_rows")
 
 
@@ -74,14 +73,10 @@ def test_fixture_lengths_are_the_test(name):
 
 
 def test_header_declares_and_the_library_exports_the_new_launchers():
-    header = open(os.path.join(ROOT, "include", "s2svc_hip.h")).read()
-    declared = set(re.findall(r"\b(s2svc_[a-z0-9_]+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build_library(verbose=False)
-    L = _lib.lib()
+    header, declared, L = abi_header.text(), abi_header.declared(), abi_header.library()
     for n in NEW:
         assert n in declared, f"{n} not declared in include/s2svc_hip.h"
-        assert n in _lib._SIGS and n in _lib.exported_symbols(), f"{n} missing from the ctypes table"
+        assert n in _lib._FUNCTIONS and n in _lib.exported_symbols(), f"{n} missing from the ctypes binding"
         assert hasattr(L, n), f"{n} not exported by the library"
     assert "convmod_infer.hip" in _lib.sources()
     assert "replaces: modules/conformer/convolution.py:68-75" in header and "modules/length_regulator.py:127-135" in header

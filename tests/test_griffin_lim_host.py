@@ -2,8 +2,6 @@
 Spectrogram2Waveform against literal expectations from the reference file, the cached pseudo-inverse, the refusals and the C ABI."""
 import importlib
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,7 +9,6 @@ import torch
 
 import griffin_lim_ref as GR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOMETRIES = [(512, 128, None), (1024, 256, None), (2048, 300, 1200), (2048, 512, None)]
 
 
@@ -154,16 +151,13 @@ def test_tables_are_float64_built_and_window_is_centred():
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
+    import abi_header
     from seq2seq_vc_amd import _lib
     names = ["s2svc_gl_supported", "s2svc_gl_prepare", "s2svc_gl_synth", "s2svc_gl_analyse", "s2svc_gl_ola"]
-    header = open(os.path.join(ROOT, "include", "s2svc_hip.h")).read()
-    declared = set(re.findall(r"\b(s2svc_[a-z0-9_]+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build_library(verbose=False)
-    L = _lib.lib()
+    declared, L = abi_header.declared(), abi_header.library()
     for n in names:
         assert n in declared, f"{n} missing from the header"
-        assert n in _lib._SIGS and n in _lib.exported_symbols(), f"{n} missing from the ctypes table"
+        assert n in _lib._FUNCTIONS and n in _lib.exported_symbols(), f"{n} missing from the ctypes binding"
         assert hasattr(L, n), f"{n} not exported by the library"
     assert [L.s2svc_gl_supported(n) for n in (256, 512, 1024, 2048, 4096, 800)] == [0, 1, 1, 1, 0, 0]
     assert "griffin_lim.hip" in _lib.sources()

@@ -2,7 +2,6 @@
 segment tables, the conditions the GPU cases rely on asserted on the very inputs they use, the power of the comparison rule against
 planted errors, and the ABI ledger.  None of this launches a kernel."""
 import inspect
-import os
 
 import numpy as np
 import pytest
@@ -13,7 +12,6 @@ import step_kernels_ref as R
 from oracle import logmel as OL
 
 F32, F64 = torch.float32, torch.float64
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- 1. interface -------------------------------------------------------------------------------------------------------------
@@ -186,15 +184,13 @@ def test_planted_errors_are_rejected(plant):
 
 # ---- 5. the ledger ------------------------------------------------------------------------------------------------------------
 def test_header_sigs_exports_and_sources():
+    import abi_header
     from seq2seq_vc_amd import _lib
     new = ["s2svc_melspec_supported", "s2svc_melspec_fwd", "s2svc_melspec_loss_finish", "s2svc_melspec_bwd_frames", "s2svc_melspec_bwd_ola"]
-    header = open(os.path.join(ROOT, "include", "s2svc_hip.h")).read()
+    header, L = abi_header.text(), abi_header.library()
     assert "melspec.hip" in _lib.sources()
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build_library(verbose=False)
-    L = _lib.lib()
     for sym in new:
-        assert (sym + "(") in header and sym in _lib._SIGS and hasattr(L, sym), sym
+        assert (sym + "(") in header and sym in _lib._FUNCTIONS and hasattr(L, sym), sym
     assert "urhythmic/dataset.py:23-50" in header
     assert L.s2svc_melspec_supported(1024, 1024, 80) == 1 and L.s2svc_melspec_supported(1024, 1024, 128) == 1
     assert L.s2svc_melspec_supported(512, 512, 80) == 0 and L.s2svc_melspec_supported(1024, 800, 80) == 0

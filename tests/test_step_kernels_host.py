@@ -353,8 +353,8 @@ LEDGER = {
 
 
 def _declared_launchers():
-    header = open(os.path.join(ROOT, "include", "s2svc_hip.h")).read()
-    return sorted(set(re.findall(r"\b(s2svc_[a-z0-9_]+)\s*\(", header)) - {"s2svc_operand", "s2svc_gemm_desc"})
+    from seq2seq_vc_amd import _lib
+    return _lib.exported_symbols()
 
 
 def _wrappers(declared):

@@ -1,7 +1,5 @@
 """Host-side checks of urhythmic (no GPU): the numpy restatement of the segmentation search against the fixture recorded from the
 reference, the rounding family, the host bookkeeping of the segmenter, rhythm model and time stretchers, the refusals and the C ABI."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ from seq2seq_vc_amd import urhythmic as U
 from seq2seq_vc_amd.ops import kernels_urhythmic as KU
 from seq2seq_vc_amd.urhythmic.stretcher import segment_table, stretch_plan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = UR.load_golden()
 KEYS = ("alpha", "P", "codes", "boundaries", "clusters", "cboundaries")
 SOUND = {c: getattr(U, n) for c, n in UR.SOUND_TYPE_OF_CLUSTER.items()}
@@ -182,16 +179,13 @@ def test_stretch_plan_applies_both_filters_and_matches_the_fixture_lengths():
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
+    import abi_header
     from seq2seq_vc_amd import _lib
     names = ["s2svc_useg_ws_bytes", "s2svc_useg_spans", "s2svc_useg_search", "s2svc_useg_stretch"]
-    header = open(os.path.join(ROOT, "include", "s2svc_hip.h")).read()
-    declared = set(re.findall(r"\b(s2svc_[a-z0-9_]+)\s*\(", header))
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build_library(verbose=False)
-    L = _lib.lib()
+    header, declared, L = abi_header.text(), abi_header.declared(), abi_header.library()
     for n in names:
         assert n in declared, f"{n} missing from the header"
-        assert (n in _lib._SIGS or n in _lib._RET64) and n in _lib.exported_symbols(), f"{n} missing from the ctypes table"
+        assert n in _lib._FUNCTIONS and n in _lib.exported_symbols(), f"{n} missing from the ctypes binding"
         assert hasattr(L, n), f"{n} not exported by the library"
     assert "urhythmic.hip" in _lib.sources()
     assert "K <= 256" in header and "Tmax <= 4096" in header
