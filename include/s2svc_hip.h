@@ -874,6 +874,57 @@ int s2svc_hifigan_conv_out_bwd(int dtype, int B, int T, int C, int k, int chunk,
                                float slope, float scale, void* dx, float* wpart, float* bpart, void* stream);
 
 /* ========================================================================================== */
+/* HiFi-GAN multi-period discriminator, forward and backward, fp32 (csrc/hifigan_disc.hip).    */
+/* One PeriodDiscriminator of period p folds x (B, 1, T) into (B, 1, L0, p), L0 = ceil(T / p)  */
+/* (reflect pad on the right), and convolves along L only.  Activations are channel-last       */
+/* (B, L, p, C) and hold the POST-activation values (they are the features the caller gets);   */
+/* a row is (b, l, w).  A convolution (k = 5, padding 2, stride s) maps L to (L - 1) / s + 1;  */
+/* rows outside [0, L) of the same (b, w) sequence are zero.  leaky_relu'(m) = 1 for m > 0,    */
+/* slope otherwise, taken from the stored output.  Weight norm: s2svc_hifigan_fold mode 0 / 2  */
+/* on the (O, C, k) view of weight_v, s2svc_hifigan_fold_bwd mode 0, and                       */
+/* s2svc_hifigan_wgrad_finish mode 0 / 2 over the partials below.  No atomics: every sum runs  */
+/* in an order fixed by the shapes.                                                            */
+/* replaces: urhythmic/vocoder.py:211-327 (PeriodDiscriminator, MultiPeriodDiscriminator) and  */
+/* loss.backward() through them (urhythmic_fine_tune_vocoder.py:191-222).                      */
+/* ========================================================================================== */
+/* Input layer 1 -> 32, k = 5, stride 3: out (B, L1, p, 32) = leaky_relu(conv(x') + bias), x' = x (B, T) reflect-padded to L0 * p
+   samples and viewed (L0, p) -- both by index arithmetic, no padded copy.  w32 [32][5] (s2svc_hifigan_fold's w32 of (32, 1, 5)).
+   replaces: urhythmic/vocoder.py:278-287 (F.pad reflect, view, convs[0], leaky_relu) */
+int s2svc_hifigan_disc_input(int B, int T, int p, const float* x, const float* w32, const float* bias, float slope, float* out,
+                             void* stream);
+/* Strided convolution as an implicit GEMM on MFMA: x (B, L, p, C_in) -> out (B, (L - 1) / stride + 1, p, C_out) =
+   leaky_relu(conv + bias); stride 1 or 3, C_in a multiple of 16, C_out of 4; w_op [C_out][5 * Cinp] (s2svc_hifigan_fold mode 0).
+   replaces: urhythmic/vocoder.py:285-288 (convs[1..4], leaky_relu) */
+int s2svc_hifigan_disc_conv(int B, int L, int p, int Cin, int Cout, int stride, const float* x, const float* w_op, const float* bias,
+                            float slope, float* out, void* stream);
+/* conv_post C -> 1, k = 3, padding 1, no activation: y (B, L * p) in (l, w) order; w [3][C] (s2svc_hifigan_fold mode 2).
+   replaces: urhythmic/vocoder.py:289-291 (conv_post, flatten) */
+int s2svc_hifigan_disc_post(int B, int L, int p, int C, const float* x, const float* w, const float* bias, float* y, void* stream);
+/* Backward of s2svc_hifigan_disc_post: d = dy1 + dy2 (each (B, L * p) or NULL: the gradients of the score and of the last feature);
+   dx (B, L, p, C) = leaky_relu'(x) * (add + the C -> 1 data gradient), add (B, L, p, C) or NULL = the gradient of the feature x itself;
+   wpart [chunks][3][C], bpart [chunks] over chunks of 256 rows of B * L * p.
+   replaces: autograd of urhythmic/vocoder.py:287-291 */
+int s2svc_hifigan_disc_post_bwd(int B, int L, int p, int C, const float* x, const float* w, const float* dy1, const float* dy2,
+                                const float* add, float slope, float* dx, float* wpart, float* bpart, void* stream);
+/* Weight / bias gradient partials of s2svc_hifigan_disc_conv: dy (B, Lo, p, C_out) = the gradient of the PRE-activation, x (B, L, p, C_in)
+   the layer's input; chunk q covers rows [256 q, 256 q + 256) of B * Lo * p: wpart [chunks][C_out][5][C_in], bpart [chunks][C_out].
+   replaces: autograd of urhythmic/vocoder.py:285-288 (weight and bias gradients of convs[1..4]) */
+int s2svc_hifigan_disc_wgrad(int B, int L, int p, int Cin, int Cout, int stride, const float* dy, const float* x, float* wpart,
+                             float* bpart, void* stream);
+/* Data gradient of s2svc_hifigan_disc_conv: dy (B, Lo, p, C_out) -> dx (B, L, p, C_in) = leaky_relu'(mask_src) * (add + conv^T(dy)),
+   mask_src / add (B, L, p, C_in) or NULL: the stored output of the layer below and the gradient of that feature.  Stride 3 is
+   phase-decomposed: row l receives only the taps j = l + 2 (mod 3).  w_opT: s2svc_hifigan_fold_bwd mode 0; C_out a multiple of 16.
+   replaces: autograd of urhythmic/vocoder.py:285-288 (data gradient of convs[1..4], leaky_relu backward) */
+int s2svc_hifigan_disc_dgrad(int B, int L, int p, int Cin, int Cout, int stride, const float* dy, const float* w_opT, const float* mask_src,
+                             const float* add, float slope, float* dx, void* stream);
+/* Weight / bias partials of the input layer: dy (B, L1, p, 32), x (B, T) -> wpart [chunks][32][5], bpart [chunks][32], chunks =
+   ceil(B * L1 * p / 256).  replaces: autograd of urhythmic/vocoder.py:278-287 (gradients of convs[0]) */
+int s2svc_hifigan_disc_input_wgrad(int B, int T, int p, const float* dy, const float* x, float* wpart, float* bpart, void* stream);
+/* dx (B, T) of the input layer: a gather -- sample t collects its own padded position and, where the reflect pad copied it, its
+   mirror image 2 (T - 1) - t.  replaces: autograd of urhythmic/vocoder.py:278-287 (F.pad reflect / view / convs[0] backward) */
+int s2svc_hifigan_disc_input_dgrad(int B, int T, int p, const float* dy, const float* w32, float* dx, void* stream);
+
+/* ========================================================================================== */
 /* Griffin-Lim phase reconstruction, fp32 (csrc/griffin_lim.hip): librosa.griffinlim with      */
 /* init="random" as vocoder/griffin_lim.py:53-106 calls it, for a batch with per-row lengths   */
 /* in 2 n_iter + 3 launches.  Buffers: S (B, Tmax, bins) fp32, X / Rprev (B, Tmax, bins)       */

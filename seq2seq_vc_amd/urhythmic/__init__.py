@@ -1,10 +1,11 @@
 """Urhythmic on HIP: segmenter, rhythm model, time stretchers and the conversion that chains them with the HiFi-GAN generator."""
 from .dataset import LogMelSpectrogram
+from .vocoder import MultiPeriodDiscriminator, PeriodDiscriminator
 from .model import UrhythmicFine
 from .rhythm_model import RhythmModelFineGrained, segment_rate, transform
 from .segmenter import Segmenter, cluster_merge, segment
 from .stretcher import TimeStretcherFineGrained, TimeStretcherGlobal
 from .utils import OBSTRUENT, SILENCE, SONORANT, SoundType
 
-__all__ = ["LogMelSpectrogram", "UrhythmicFine", "RhythmModelFineGrained", "segment_rate", "transform", "Segmenter", "cluster_merge", "segment",
+__all__ = ["LogMelSpectrogram", "MultiPeriodDiscriminator", "PeriodDiscriminator", "UrhythmicFine", "RhythmModelFineGrained", "segment_rate", "transform", "Segmenter", "cluster_merge", "segment",
            "TimeStretcherFineGrained", "TimeStretcherGlobal", "OBSTRUENT", "SILENCE", "SONORANT", "SoundType"]

@@ -1,0 +1,253 @@
+"""HiFi-GAN multi-period discriminator on the HIP kernels of csrc/hifigan_disc.hip, forward and backward, fp32.
+
+Drop-in surface of the reference's `seq2seq_vc/urhythmic/vocoder.py` PeriodDiscriminator / MultiPeriodDiscriminator (:211-327): the
+constructor arguments, the `state_dict` keys and shapes (`discriminators.{i}.convs.{j}.{bias,weight_g,weight_v}`, `conv_post.*`,
+weights (O, C, k, 1)) and the call `forward(x (B, 1, T)) -> (score, feats)`; `discriminator.mpd = MultiPeriodDiscriminator()` plus
+`load_state_dict` of the checkpoint's `mpd.*` subtree puts it into the reference's HifiganDiscriminator.  The multi-scale
+discriminator, the three loss functions and the optimiser stay the caller's stock torch code.
+
+Activations are channel-last (B, L, p, C); the features handed out are strided (B, C, L, p) views of them and the score is the
+flattening of the last one.  Under grad mode a PeriodDiscriminator call is ONE autograd node whose inputs are x and the 18
+parameters and whose outputs are the score and the six features; its backward takes whichever of the seven gradients arrive, in
+any strides (channel-last-strided ones are read in place, others go through one copy), and returns the parameter gradients and --
+when x requires grad -- dx, which flows on into `HifiganGenerator.trainable()`.  There is no CPU path and no bf16 path: a bf16
+forward flips leaky-relu masks, which alone puts the gradients several per cent off.
+`launch_plan()` / `backward_plan()` list the launches of one call."""
+import math
+
+import torch
+from torch import nn
+
+from ..ops import kernels_disc as KD
+from ..ops import kernels_vocoder as KV
+
+LRELU_SLOPE = 0.1
+PERIODS = (2, 3, 5, 7, 11)
+CHANNELS = (1, 32, 128, 512, 1024, 1024)          # convs[j]: CHANNELS[j] -> CHANNELS[j + 1]
+STRIDES = (3, 3, 3, 3, 1)
+KINDS = ("fold", "input", "conv", "post")
+BWD_KINDS = ("post_bwd", "wgrad", "input_wgrad", "finish", "fold_bwd", "dgrad", "input_dgrad")
+
+
+class _WNConv2d(nn.Module):
+    """Parameters of weight_norm(Conv2d(cin, cout, (k, 1))) in the reference's checkpoint form, torch's default initialisation."""
+
+    def __init__(self, cin, cout, k):
+        super().__init__()
+        bound = 1.0 / math.sqrt(cin * k)
+        v = torch.empty(cout, cin, k, 1).uniform_(-bound, bound)
+        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1, 1))
+        self.weight_v = nn.Parameter(v)
+
+    def vg(self):
+        """(v (O, C, k), g (O)) fp32 contiguous views of the live parameters"""
+        v = self.weight_v.detach()
+        return v.contiguous().view(v.shape[0], v.shape[1], v.shape[2]), self.weight_g.detach().contiguous().view(-1)
+
+
+def layer_lengths(T, p):
+    """[L0, L1, .., L5]: rows along L of the folded input and of the output of convs[0..4] (conv_post keeps L5)."""
+    L = [KD.folded_len(T, p)[0]]
+    for s in STRIDES:
+        L.append(KD.out_len(L[-1], s))
+    return L
+
+
+class _PeriodFunction(torch.autograd.Function):
+    """One PeriodDiscriminator call as ONE autograd node: inputs x and the 18 parameters, outputs the score and the six features."""
+
+    @staticmethod
+    def forward(ctx, disc, x, *params):
+        ctx.set_materialize_grads(False)
+        score, feats, state = disc._run(x, keep=True)
+        ctx.disc, ctx.state = disc, state
+        ctx.save_for_backward(*params)           # autograd refuses a backward after an in-place update of one of them
+        return (score,) + tuple(feats)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gscore, *gfeats):
+        ctx.saved_tensors                        # the version check of the parameters
+        need_dx, need_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        dx, grads = ctx.disc._backward(ctx.state, gscore, gfeats, need_dx, need_params)
+        return (None, dx) + tuple(grads)
+
+
+class PeriodDiscriminator(nn.Module):
+    """HiFi-GAN period discriminator (reference urhythmic/vocoder.py:211-293).  x (B, 1, T) fp32 on the device ->
+    (score (B, L5 * p), [six features (B, C, L, p)])."""
+
+    def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
+        super().__init__()
+        if use_spectral_norm:
+            raise NotImplementedError("PeriodDiscriminator: spectral norm is not implemented (the multi-period discriminator never sets it)")
+        if kernel_size != KD.TAPS or stride != KD.STRIDE:
+            raise ValueError(f"PeriodDiscriminator: the kernels are built for kernel_size {KD.TAPS}, stride {KD.STRIDE} (csrc/hifigan_disc.hip)")
+        if int(period) < 1:
+            raise ValueError("PeriodDiscriminator: period >= 1")
+        self.period = int(period)
+        self.convs = nn.ModuleList([_WNConv2d(CHANNELS[j], CHANNELS[j + 1], kernel_size) for j in range(len(STRIDES))])
+        self.conv_post = _WNConv2d(CHANNELS[-1], 1, KD.POST_TAPS)
+
+    # ---- the launch lists -------------------------------------------------------------------------------------------------
+    def launch_plan(self):
+        """What one forward call launches, in order: dicts with `kind` in KINDS: 12 per period, 60 per MultiPeriodDiscriminator call.
+        forward() executes exactly this list.  ("fold" is the fold kernel; hifigan_fold zero-fills each of the five operand buffers with
+        one more library launch beside it, and hifigan_fold_bwd does the same in the backward: 17 and 25 / 24 launches per period.)"""
+        plan = [dict(kind="fold", layer=f"convs.{j}", mode=0) for j in range(len(STRIDES))] + [dict(kind="fold", layer="conv_post", mode=2)]
+        plan.append(dict(kind="input", layer="convs.0", dst=0, cout=CHANNELS[1], stride=STRIDES[0]))
+        for j in range(1, len(STRIDES)):
+            plan.append(dict(kind="conv", layer=f"convs.{j}", src=j - 1, dst=j, cin=CHANNELS[j], cout=CHANNELS[j + 1], stride=STRIDES[j]))
+        plan.append(dict(kind="post", layer="conv_post", src=len(STRIDES) - 1, dst=len(STRIDES), cin=CHANNELS[-1]))
+        return plan
+
+    def backward_plan(self, need_dx=False, need_params=True):
+        """What one backward pass launches, in order: dicts with `kind` in BWD_KINDS.  Per layer from the top: the weight / bias
+        partials and their finish launch (when a parameter needs a gradient), then the data gradient, whose epilogue adds the gradient
+        of the feature below and applies its leaky_relu'.  The input layer's data gradient runs only when x requires grad.
+        _backward() executes exactly this list."""
+        n = len(STRIDES)
+        plan = [dict(kind="post_bwd", layer="conv_post", src=n - 1)]
+        if need_params:
+            plan.append(dict(kind="finish", layer="conv_post", mode=2))
+        for j in range(n - 1, 0, -1):
+            if need_params:
+                plan += [dict(kind="wgrad", layer=f"convs.{j}", src=j - 1, stride=STRIDES[j]), dict(kind="finish", layer=f"convs.{j}", mode=0)]
+            plan += [dict(kind="fold_bwd", layer=f"convs.{j}"),
+                     dict(kind="dgrad", layer=f"convs.{j}", mask=j - 1, cin=CHANNELS[j], stride=STRIDES[j])]
+        if need_params:
+            plan += [dict(kind="input_wgrad", layer="convs.0"), dict(kind="finish", layer="convs.0", mode=0)]
+        if need_dx:
+            plan.append(dict(kind="input_dgrad", layer="convs.0"))
+        return plan
+
+    # ---- execution --------------------------------------------------------------------------------------------------------
+    def _leaf(self, name):
+        return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
+
+    def _check(self, x):
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"PeriodDiscriminator: x (B, 1, T) expected, got {tuple(x.shape)}")
+        dtypes = {x.dtype} | {p.dtype for p in self.parameters()}
+        if torch.bfloat16 in dtypes or torch.float16 in dtypes:
+            raise NotImplementedError("PeriodDiscriminator runs in fp32 only: a 16-bit forward flips leaky-relu masks, which alone puts the "
+                                      "gradients several per cent off (DESIGN.md section 8)")
+        if dtypes != {torch.float32}:
+            raise TypeError("PeriodDiscriminator: float32 input and parameters")
+        if not x.is_cuda or not self.conv_post.bias.is_cuda:
+            raise RuntimeError("PeriodDiscriminator needs GPU tensors and GPU parameters (there is no CPU path)")
+        KD.folded_len(x.shape[2], self.period)
+
+    def _run(self, x, keep=False):
+        """-> (score, feats, state).  keep: also what the backward reads (the folded weights, the parameters' views, the input)."""
+        B, _, T = x.shape
+        p = self.period
+        with torch.no_grad():
+            x2 = x.detach().reshape(B, T).contiguous()
+            ops, bufs, state = {}, {}, {}
+            for e in self.launch_plan():
+                kind, layer = e["kind"], e["layer"]
+                if kind == "fold":
+                    v, g = self._leaf(layer).vg()
+                    first = layer == "convs.0"
+                    w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=first or (keep and e["mode"] == 0), want_op=not first)
+                    ops[layer] = (w32, op, self._leaf(layer).bias.detach().contiguous(), v, g)
+                    continue
+                w32, op, bias = ops[layer][:3]
+                if kind == "input":
+                    bufs[e["dst"]] = KD.disc_input(x2, w32, bias, p, slope=LRELU_SLOPE)
+                elif kind == "conv":
+                    bufs[e["dst"]] = KD.disc_conv(bufs[e["src"]], op, bias, e["cout"], e["stride"], slope=LRELU_SLOPE)
+                else:
+                    src = bufs[e["src"]]
+                    bufs[e["dst"]] = KD.disc_post(src, op, bias).view(B, src.shape[1], p, 1)
+            n = len(STRIDES)
+            feats = [bufs[j].permute(0, 3, 1, 2) for j in range(n + 1)]
+            score = bufs[n].view(B, -1)
+            if keep:
+                state = dict(ops=ops, bufs=bufs, x=x2, T=T)
+        return score, feats, state
+
+    def _backward(self, state, gscore, gfeats, need_dx, need_params):
+        """(dx or None, the 18 parameter gradients in named_parameters() order or Nones) from whichever of the seven output gradients
+        arrived: executes backward_plan()."""
+        ops, bufs, x2, T = state["ops"], state["bufs"], state["x"], state["T"]
+        p, n = self.period, len(STRIDES)
+        B = x2.shape[0]
+
+        def channel_last(g):
+            """a (B, C, L, p) gradient as contiguous (B, L, p, C): in place when it already is channel-last-strided, else one copy"""
+            if g is None:
+                return None
+            g = g.detach().float().permute(0, 2, 3, 1)
+            return g if g.is_contiguous() else g.contiguous()
+
+        def flat(g):
+            return None if g is None else g.detach().float().reshape(B, -1).contiguous()
+
+        gf = [channel_last(g) for g in gfeats[:n]]
+        out, parts, dpre, opT, dx = {}, None, None, None, None
+        with torch.no_grad():
+            for e in self.backward_plan(need_dx, need_params):
+                kind, layer = e["kind"], e["layer"]
+                w32, op, _, v, g = ops[layer]
+                if kind == "post_bwd":
+                    dpre, wp, bp = KD.disc_post_bwd(bufs[e["src"]], op, dy1=flat(gscore), dy2=flat(gfeats[n]), add=gf[e["src"]], slope=LRELU_SLOPE)
+                    parts = (wp, bp)
+                elif kind == "wgrad":
+                    parts = KD.disc_wgrad(dpre, bufs[e["src"]], e["stride"])
+                elif kind == "input_wgrad":
+                    parts = KD.disc_input_wgrad(dpre, x2, p)
+                elif kind == "finish":
+                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], v, g)
+                    parts = None
+                elif kind == "fold_bwd":
+                    opT = KV.hifigan_fold_bwd(0, w32, torch.float32)
+                elif kind == "dgrad":
+                    mask = bufs[e["mask"]]
+                    dpre = KD.disc_dgrad(dpre, opT, mask.shape[1], e["cin"], e["stride"], mask_src=mask, add=gf[e["mask"]], slope=LRELU_SLOPE)
+                    opT = None
+                else:
+                    dx = KD.disc_input_dgrad(dpre, w32, T, p).view(B, 1, T)
+        grads = []
+        for name, prm in self.named_parameters():
+            if not need_params:
+                grads.append(None)
+                continue
+            layer, leaf = name.rsplit(".", 1)
+            gw, gg, gb = out[layer]
+            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
+        return dx, grads
+
+    def forward(self, x):
+        self._check(x)
+        params = [prm for _, prm in self.named_parameters()]
+        if torch.is_grad_enabled() and (x.requires_grad or any(prm.requires_grad for prm in params)):
+            res = _PeriodFunction.apply(self, x, *params)
+            return res[0], list(res[1:])
+        score, feats, _ = self._run(x)
+        return score, feats
+
+
+class MultiPeriodDiscriminator(nn.Module):
+    """HiFi-GAN multi-period discriminator (reference urhythmic/vocoder.py:296-327): five PeriodDiscriminators, periods 2, 3, 5, 7, 11.
+    x (B, 1, T) -> ([five scores], [five lists of six features])."""
+
+    def __init__(self):
+        super().__init__()
+        self.discriminators = nn.ModuleList([PeriodDiscriminator(p) for p in PERIODS])
+
+    def launch_plan(self):
+        return [dict(e, period=d.period) for d in self.discriminators for e in d.launch_plan()]
+
+    def backward_plan(self, need_dx=False, need_params=True):
+        return [dict(e, period=d.period) for d in self.discriminators for e in d.backward_plan(need_dx, need_params)]
+
+    def forward(self, x):
+        scores, feats = [], []
+        for d in self.discriminators:
+            score, feat = d(x)
+            scores.append(score)
+            feats.append(feat)
+        return scores, feats
