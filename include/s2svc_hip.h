@@ -925,6 +925,78 @@ int s2svc_hifigan_disc_input_wgrad(int B, int T, int p, const float* dy, const f
 int s2svc_hifigan_disc_input_dgrad(int B, int T, int p, const float* dy, const float* w32, float* dx, void* stream);
 
 /* ========================================================================================== */
+/* HiFi-GAN multi-scale discriminator, forward and backward, fp32 (csrc/hifigan_msd.hip).      */
+/* Three ScaleDiscriminators see x (B, 1, T), pool(x) and pool(pool(x)).  Activations are      */
+/* channel-last (B, L, C) and hold the POST-activation values (the features the caller gets).  */
+/* A convolution (k taps, padding (k - 1) / 2, stride s) maps L to (L - 1) / s + 1; rows       */
+/* outside [0, L) of an utterance are zero and a column tile lies inside one group.            */
+/* leaky_relu'(m) = 1 for m > 0, slope otherwise, taken from the stored output.  Weight norm   */
+/* (scales 1, 2): s2svc_hifigan_fold mode 0 / 2 on weight_v (O, C / groups, k) and             */
+/* s2svc_hifigan_wgrad_finish mode 0 / 2 over the partials.  Spectral norm (scale 0): the      */
+/* s2svc_hifigan_msd_sn_* launches and the same fold / finish with g = NULL.  Layer 6          */
+/* (1024 -> 1024, 5 taps) and conv_post are s2svc_hifigan_disc_conv / _dgrad / _wgrad / _post  */
+/* / _post_bwd at p = 1.  No atomics: every sum runs in an order fixed by the shapes.          */
+/* replaces: urhythmic/vocoder.py:330-402 (ScaleDiscriminator, MultiScaleDiscriminator) and    */
+/* loss.backward() through them (urhythmic_fine_tune_vocoder.py:191-222).                      */
+/* ========================================================================================== */
+/* AvgPool1d(4, 2, padding 2), the padding counted: y (B, T / 2 + 1), y[t] = 0.25 * sum_{j < 4} x[2 t - 2 + j], zeros outside x (B, T).
+   replaces: urhythmic/vocoder.py:380-398 (meanpools) */
+int s2svc_hifigan_msd_pool(int B, int T, const float* x, float* y, void* stream);
+/* Its adjoint: dx (B, T) from dy (B, T / 2 + 1), a gather with one lane per sample.
+   replaces: autograd of urhythmic/vocoder.py:380-398 */
+int s2svc_hifigan_msd_pool_bwd(int B, int T, const float* dy, float* dx, void* stream);
+/* Input layer 1 -> 128, k = 15, padding 7: out (B, T, 128) = leaky_relu(conv(x) + bias), x (B, T); w32 [128][15].
+   replaces: urhythmic/vocoder.py:338, 358-361 (convs[0], leaky_relu) */
+int s2svc_hifigan_msd_input(int B, int T, const float* x, const float* w32, const float* bias, float slope, float* out, void* stream);
+/* Weight / bias partials of the input layer: dy (B, T, 128), x (B, T) -> wpart [chunks][128][15], bpart [chunks][128], chunks =
+   ceil(B * T / 256).  replaces: autograd of urhythmic/vocoder.py:338 (gradients of convs[0]) */
+int s2svc_hifigan_msd_input_wgrad(int B, int T, const float* dy, const float* x, float* wpart, float* bpart, void* stream);
+/* dx (B, T) of the input layer: sample t gathers dy[t + 7 - j] . w[:, j] over the 15 taps, one wavefront per sample.
+   replaces: autograd of urhythmic/vocoder.py:338 (data gradient of convs[0]) */
+int s2svc_hifigan_msd_input_dgrad(int B, int T, const float* dy, const float* w32, float* dx, void* stream);
+/* Grouped strided convolution, k = 41, padding 20, as an implicit GEMM on MFMA: x (B, L, C_in) -> out (B, (L - 1) / stride + 1, C_out)
+   = leaky_relu(conv + bias); stride 1, 2 or 4; C_in / groups and C_out / groups multiples of 4, at most 64.
+   w_op [C_out][41 * Cgp]: s2svc_hifigan_fold mode 0 of the weight (C_out, C_in / groups, 41), Cgp = C_in / groups padded to 32.
+   replaces: urhythmic/vocoder.py:339-343, 358-361 (convs[1..5], leaky_relu) */
+int s2svc_hifigan_msd_gconv(int B, int L, int Cin, int Cout, int groups, int stride, const float* x, const float* w_op, const float* bias,
+                            float slope, float* out, void* stream);
+/* Operand of the data gradient from the folded weight w32 (C_out, C_in / groups, 41): w_opT [C_in][41 * Ogp],
+   [(g, c)][j * Ogp + o] = w32[g * Og + o][c][j], Og = C_out / groups, Ogp = Og padded to 32 (the padding is written as zero).
+   replaces: autograd of urhythmic/vocoder.py:339-343 (the transposed weight of the data gradient) */
+int s2svc_hifigan_msd_fold_bwd(int Cin, int Cout, int groups, const float* w32, float* w_opT, void* stream);
+/* Data gradient of s2svc_hifigan_msd_gconv: dy (B, Lo, C_out) -> dx (B, L, C_in) = leaky_relu'(mask_src) * (add + conv^T(dy)),
+   mask_src / add (B, L, C_in) or NULL: the stored output of the layer below and the gradient of that feature.  Phase-decomposed:
+   row l receives only the taps j = l + 20 (mod stride), one grid plane per phase.
+   replaces: autograd of urhythmic/vocoder.py:339-343 (data gradient of convs[1..5], leaky_relu backward) */
+int s2svc_hifigan_msd_gconv_dgrad(int B, int L, int Cin, int Cout, int groups, int stride, const float* dy, const float* w_opT,
+                                  const float* mask_src, const float* add, float slope, float* dx, void* stream);
+/* Rows per partial of s2svc_hifigan_msd_gconv_wgrad for Lo output rows per utterance: max(256, 32 * ceil(Lo / 256)) -- at most
+   eight partials per utterance and never fewer than one: at 8 x 8320 samples 43 MB for layers 1 and 4, 86 MB for layer 5
+   (8 utterances x 10.7 MB, one chunk each), which the finish launch streams.
+   replaces: nothing (the sizing rule both sides of the ABI share) */
+int s2svc_hifigan_msd_gconv_chunk(int Lo);
+/* Weight / bias gradient partials of s2svc_hifigan_msd_gconv: dy (B, Lo, C_out) = the gradient of the PRE-activation, x (B, L, C_in)
+   the layer's input; every utterance is cut on its own into ceil(Lo / chunk) chunks of `chunk` output rows
+   (= s2svc_hifigan_msd_gconv_chunk(Lo)): wpart [B * chunks][C_out][41][C_in / groups], bpart [B * chunks][C_out]; summed by
+   s2svc_hifigan_wgrad_finish mode 0 with D1 = C_in / groups, k = 41.
+   replaces: autograd of urhythmic/vocoder.py:339-343 (weight and bias gradients of convs[1..5]) */
+int s2svc_hifigan_msd_gconv_wgrad(int B, int L, int Cin, int Cout, int groups, int stride, int chunk, const float* dy, const float* x,
+                                  float* wpart, float* bpart, void* stream);
+/* Spectral norm, W (O, K) = weight_orig viewed from dim 0.  iterate: v = W^T u / max(|W^T u|, eps), u = W v / max(|W v|, eps), both in
+   place; then sigma[0] = u . (W v) on the device.  iterate = 0 leaves u, v untouched.  Norms and dot products in double; ws: K + O doubles.
+   replaces: torch.nn.utils.spectral_norm's compute_weight as urhythmic/vocoder.py:335-347 uses it (one power iteration, eps 1e-12) */
+int s2svc_hifigan_msd_sn_power(int O, int K, int iterate, float eps, const float* W, float* u, float* v, float* sigma, double* ws,
+                               void* stream);
+/* w = W / sigma[0], n values (the weight the convolutions of the spectrally normed scale use).
+   replaces: torch.nn.utils.spectral_norm's weight = weight_orig / sigma */
+int s2svc_hifigan_msd_sn_scale(int64_t n, const float* W, const float* sigma, float* w, void* stream);
+/* Backward of the division with u, v constant: grad (O, K) = dW / sigma - (sum(dW o W) / sigma^2) u v^T, dW = the gradient of
+   W / sigma (the summed partials); the sum in double; ws: O doubles.
+   replaces: autograd through torch.nn.utils.spectral_norm (urhythmic/vocoder.py:335-347) */
+int s2svc_hifigan_msd_sn_finish(int O, int K, const float* dW, const float* W, const float* u, const float* v, const float* sigma,
+                                float* grad, double* ws, void* stream);
+
+/* ========================================================================================== */
 /* Griffin-Lim phase reconstruction, fp32 (csrc/griffin_lim.hip): librosa.griffinlim with      */
 /* init="random" as vocoder/griffin_lim.py:53-106 calls it, for a batch with per-row lengths   */
 /* in 2 n_iter + 3 launches.  Buffers: S (B, Tmax, bins) fp32, X / Rprev (B, Tmax, bins)       */

@@ -1,10 +1,18 @@
-"""HiFi-GAN multi-period discriminator on the HIP kernels of csrc/hifigan_disc.hip, forward and backward, fp32.
+"""HiFi-GAN discriminator on the HIP kernels of csrc/hifigan_disc.hip and csrc/hifigan_msd.hip, forward and backward, fp32: the
+multi-period half, the multi-scale half and HifiganDiscriminator, which holds both.
 
-Drop-in surface of the reference's `seq2seq_vc/urhythmic/vocoder.py` PeriodDiscriminator / MultiPeriodDiscriminator (:211-327): the
-constructor arguments, the `state_dict` keys and shapes (`discriminators.{i}.convs.{j}.{bias,weight_g,weight_v}`, `conv_post.*`,
-weights (O, C, k, 1)) and the call `forward(x (B, 1, T)) -> (score, feats)`; `discriminator.mpd = MultiPeriodDiscriminator()` plus
-`load_state_dict` of the checkpoint's `mpd.*` subtree puts it into the reference's HifiganDiscriminator.  The multi-scale
-discriminator, the three loss functions and the optimiser stay the caller's stock torch code.
+Drop-in surface of the reference's `seq2seq_vc/urhythmic/vocoder.py` PeriodDiscriminator / MultiPeriodDiscriminator (:211-327),
+ScaleDiscriminator / MultiScaleDiscriminator (:330-402) and HifiganDiscriminator (:405-425): the constructor arguments, the
+`state_dict` keys and shapes (`discriminators.{i}.convs.{j}.{bias,weight_g,weight_v}`, `conv_post.*`, weights (O, C, k, 1) in the
+period discriminators and (O, C / groups, k) in the scale discriminators; the spectrally normed first scale holds `bias, weight_orig`
+and the buffers `weight_u, weight_v`) and the call `forward(x (B, 1, T)) -> (scores, feats)`; a reference checkpoint of the whole
+discriminator, or its `mpd.*` / `msd.*` subtree, loads as it is.  The three loss functions and the optimiser stay the caller's stock
+torch code.
+
+A ScaleDiscriminator call is ONE autograd node as well (inputs x and its 16 or 24 parameters, outputs the score and eight features);
+the average pool between the scales is a small node of its own.  The spectrally normed scale runs one power iteration per call in
+train() mode (under no_grad too) and writes u, v back into its buffers, as torch.nn.utils.spectral_norm does; the state kept for
+the backward holds copies of the u, v and sigma that the call used.
 
 Activations are channel-last (B, L, p, C); the features handed out are strided (B, C, L, p) views of them and the score is the
 flattening of the last one.  Under grad mode a PeriodDiscriminator call is ONE autograd node whose inputs are x and the 18
@@ -19,6 +27,7 @@ import torch
 from torch import nn
 
 from ..ops import kernels_disc as KD
+from ..ops import kernels_msd as KM
 from ..ops import kernels_vocoder as KV
 
 LRELU_SLOPE = 0.1
@@ -251,3 +260,340 @@ class MultiPeriodDiscriminator(nn.Module):
             scores.append(score)
             feats.append(feat)
         return scores, feats
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the multi-scale half (csrc/hifigan_msd.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+# convs[j]: (C_in, C_out, kernel size, stride, groups); the last entry is conv_post
+MSD_LAYERS = ((1, 128, 15, 1, 1), (128, 128, 41, 2, 4), (128, 256, 41, 2, 16), (256, 512, 41, 4, 16), (512, 1024, 41, 4, 16),
+              (1024, 1024, 41, 1, 16), (1024, 1024, 5, 1, 1), (1024, 1, 3, 1, 1))
+MSD_KINDS = ("sn_power", "sn_scale", "fold", "input", "gconv", "conv", "post")
+MSD_BWD_KINDS = ("post_bwd", "wgrad", "gconv_wgrad", "input_wgrad", "finish", "sn_finish", "fold_bwd", "gfold_bwd", "dgrad", "gconv_dgrad",
+                 "input_dgrad")
+
+
+def scale_lengths(T):
+    """[L0 .. L7]: rows of the output of convs[0..6] of a ScaleDiscriminator on T samples (conv_post keeps L6)."""
+    L, out = T, []
+    for _, _, _, s, _ in MSD_LAYERS[:-1]:
+        L = KM.out_len(L, s)
+        out.append(L)
+    return out + [L]
+
+
+class _WNConv1d(nn.Module):
+    """Parameters of weight_norm(Conv1d(cin, cout, k, groups=groups)) in the reference's checkpoint form, torch's default initialisation."""
+
+    def __init__(self, cin, cout, k, groups=1):
+        super().__init__()
+        bound = 1.0 / math.sqrt(cin // groups * k)
+        v = torch.empty(cout, cin // groups, k).uniform_(-bound, bound)
+        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
+        self.weight_v = nn.Parameter(v)
+
+
+class _SNConv1d(nn.Module):
+    """Parameters and buffers of torch.nn.utils.spectral_norm(Conv1d(cin, cout, k, groups=groups)) (the hook form: dim 0, one power
+    iteration, eps 1e-12) in the reference's checkpoint form; u and v are normalised normal draws."""
+
+    def __init__(self, cin, cout, k, groups=1):
+        super().__init__()
+        bound = 1.0 / math.sqrt(cin // groups * k)
+        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
+        self.weight_orig = nn.Parameter(torch.empty(cout, cin // groups, k).uniform_(-bound, bound))
+        self.register_buffer("weight_u", torch.nn.functional.normalize(torch.randn(cout), dim=0, eps=KM.SN_EPS))
+        self.register_buffer("weight_v", torch.nn.functional.normalize(torch.randn(cin // groups * k), dim=0, eps=KM.SN_EPS))
+
+
+class _ScaleFunction(torch.autograd.Function):
+    """One ScaleDiscriminator call as ONE autograd node: inputs x and the 16 or 24 parameters, outputs the score and the eight features."""
+
+    @staticmethod
+    def forward(ctx, disc, x, *params):
+        ctx.set_materialize_grads(False)
+        score, feats, state = disc._run(x, keep=True)
+        ctx.disc, ctx.state = disc, state
+        ctx.save_for_backward(*params)           # autograd refuses a backward after an in-place update of one of them
+        return (score,) + tuple(feats)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gscore, *gfeats):
+        ctx.saved_tensors                        # the version check of the parameters
+        need_dx, need_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        dx, grads = ctx.disc._backward(ctx.state, gscore, gfeats, need_dx, need_params)
+        return (None, dx) + tuple(grads)
+
+
+class _PoolFunction(torch.autograd.Function):
+    """AvgPool1d(4, 2, padding=2) on (B, 1, T): the HIP forward and its adjoint."""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, _, T = x.shape
+        ctx.T = T
+        return KM.msd_pool(x.detach().reshape(B, T).contiguous()).view(B, 1, -1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        B = gy.shape[0]
+        return KM.msd_pool_bwd(gy.detach().float().reshape(B, -1).contiguous(), ctx.T).view(B, 1, ctx.T)
+
+
+class _MeanPool(nn.Module):
+    """AvgPool1d(4, 2, padding=2) between the scales (no parameters, as in the reference's `meanpools`)."""
+
+    def forward(self, x):
+        return _PoolFunction.apply(x)
+
+
+class ScaleDiscriminator(nn.Module):
+    """HiFi-GAN scale discriminator (reference urhythmic/vocoder.py:330-365).  x (B, 1, T) fp32 on the device ->
+    (score (B, L), [eight features (B, C, L)])."""
+
+    def __init__(self, use_spectral_norm=False):
+        super().__init__()
+        self.use_spectral_norm = bool(use_spectral_norm)
+        leaf = _SNConv1d if self.use_spectral_norm else _WNConv1d
+        self.convs = nn.ModuleList([leaf(cin, cout, k, g) for cin, cout, k, _, g in MSD_LAYERS[:-1]])
+        self.conv_post = leaf(*MSD_LAYERS[-1][:3])
+
+    # ---- the launch lists -------------------------------------------------------------------------------------------------
+    def launch_plan(self):
+        """What one forward call launches, in order: dicts with `kind` in MSD_KINDS; forward() executes exactly this list.  Weight norm:
+        one fold per layer (the input layer needs the folded weight alone, `op` False).  Spectral norm: the power iteration (or, in
+        eval() mode, sigma from the stored u, v), W / sigma, and the fold of that with g = None.  ("sn_power" is 4 small kernels with
+        `iterate`, 2 without; hifigan_fold zero-fills each operand buffer with one more library launch beside it.)"""
+        plan, n = [], len(MSD_LAYERS) - 1
+        for j in range(n + 1):
+            layer = f"convs.{j}" if j < n else "conv_post"
+            if self.use_spectral_norm:
+                plan += [dict(kind="sn_power", layer=layer, iterate=self.training), dict(kind="sn_scale", layer=layer)]
+                if j == 0:
+                    continue
+            plan.append(dict(kind="fold", layer=layer, mode=2 if j == n else 0, op=j > 0))
+        for j, (cin, cout, k, s, g) in enumerate(MSD_LAYERS[:-1]):
+            kind = "input" if j == 0 else ("gconv" if k == KM.TAPS else "conv")
+            plan.append(dict(kind=kind, layer=f"convs.{j}", src=j - 1, dst=j, cin=cin, cout=cout, stride=s, groups=g))
+        plan.append(dict(kind="post", layer="conv_post", src=n - 1, dst=n, cin=MSD_LAYERS[-1][0]))
+        return plan
+
+    def backward_plan(self, need_dx=False, need_params=True):
+        """What one backward pass launches, in order: dicts with `kind` in MSD_BWD_KINDS.  Per layer from the top: the weight / bias
+        partials, their finish launch and -- under spectral norm -- the backward of the division by sigma (when a parameter needs a
+        gradient), then the transposed operand and the data gradient, whose epilogue adds the gradient of the feature below and applies
+        its leaky_relu'.  The input layer's data gradient runs only when x requires grad.  _backward() executes exactly this list."""
+        n = len(MSD_LAYERS) - 1
+        sn = [dict(kind="sn_finish")] if self.use_spectral_norm else []
+
+        def params(layer, first, mode=0):
+            return [first, dict(kind="finish", layer=layer, mode=mode)] + [dict(e, layer=layer) for e in sn] if need_params else []
+
+        plan = [dict(kind="post_bwd", layer="conv_post", src=n - 1)]
+        plan += params("conv_post", None, 2)[1:]
+        for j in range(n - 1, 0, -1):
+            cin, cout, k, s, g = MSD_LAYERS[j]
+            grouped = k == KM.TAPS
+            layer = f"convs.{j}"
+            plan += params(layer, dict(kind="gconv_wgrad" if grouped else "wgrad", layer=layer, src=j - 1, stride=s, groups=g))
+            plan += [dict(kind="gfold_bwd" if grouped else "fold_bwd", layer=layer, groups=g),
+                     dict(kind="gconv_dgrad" if grouped else "dgrad", layer=layer, mask=j - 1, cin=cin, stride=s, groups=g)]
+        plan += params("convs.0", dict(kind="input_wgrad", layer="convs.0"))
+        if need_dx:
+            plan.append(dict(kind="input_dgrad", layer="convs.0"))
+        return plan
+
+    # ---- execution --------------------------------------------------------------------------------------------------------
+    def _leaf(self, name):
+        return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
+
+    def _check(self, x):
+        if x.dim() != 3 or x.shape[1] != 1 or x.shape[2] < 1:
+            raise ValueError(f"ScaleDiscriminator: x (B, 1, T) expected, got {tuple(x.shape)}")
+        dtypes = {x.dtype} | {p.dtype for p in self.parameters()} | {b.dtype for b in self.buffers()}
+        if torch.bfloat16 in dtypes or torch.float16 in dtypes:
+            raise NotImplementedError("ScaleDiscriminator runs in fp32 only: a 16-bit forward flips leaky-relu masks, which alone puts the "
+                                      "gradients several per cent off (DESIGN.md section 8)")
+        if dtypes != {torch.float32}:
+            raise TypeError("ScaleDiscriminator: float32 input and parameters")
+        if not x.is_cuda or not self.conv_post.bias.is_cuda:
+            raise RuntimeError("ScaleDiscriminator needs GPU tensors and GPU parameters (there is no CPU path)")
+
+    def _run(self, x, keep=False):
+        """-> (score, feats, state).  keep: also what the backward reads (the folded weights, the parameters' views, the input, and
+        copies of the u, v, sigma this call used)."""
+        B, _, T = x.shape
+        with torch.no_grad():
+            x2 = x.detach().reshape(B, T).contiguous()
+            ops, bufs, state = {}, {}, {}
+            for e in self.launch_plan():
+                kind, layer = e["kind"], e["layer"]
+                leaf = self._leaf(layer)
+                if kind == "sn_power":
+                    W = leaf.weight_orig.detach().contiguous()
+                    sigma = KM.msd_sn_power(W, leaf.weight_u, leaf.weight_v, e["iterate"])
+                    ops[layer] = dict(v=W, g=None, bias=leaf.bias.detach().contiguous(), sigma=sigma,
+                                      uv=(leaf.weight_u.clone(), leaf.weight_v.clone()) if keep else None)
+                    continue
+                if kind == "sn_scale":
+                    ops[layer]["w32"] = KM.msd_sn_scale(ops[layer]["v"], ops[layer]["sigma"])
+                    continue
+                if kind == "fold":
+                    if self.use_spectral_norm:
+                        o = ops[layer]
+                        o["op"] = KV.hifigan_fold(e["mode"], o["w32"], None, torch.float32, want_w32=False)[1]
+                    else:
+                        v, g = leaf.weight_v.detach().contiguous(), leaf.weight_g.detach().contiguous().view(-1)
+                        w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=not e["op"] or (keep and e["mode"] == 0), want_op=e["op"])
+                        ops[layer] = dict(v=v, g=g, bias=leaf.bias.detach().contiguous(), w32=w32, op=op)
+                    continue
+                o = ops[layer]
+                if kind == "input":
+                    bufs[e["dst"]] = KM.msd_input(x2, o["w32"], o["bias"], slope=LRELU_SLOPE)
+                elif kind == "gconv":
+                    bufs[e["dst"]] = KM.msd_gconv(bufs[e["src"]], o["op"], o["bias"], e["cout"], e["groups"], e["stride"], slope=LRELU_SLOPE)
+                elif kind == "conv":
+                    bufs[e["dst"]] = KD.disc_conv(bufs[e["src"]].unsqueeze(2), o["op"], o["bias"], e["cout"], e["stride"], slope=LRELU_SLOPE).squeeze(2)
+                else:
+                    src = bufs[e["src"]]
+                    bufs[e["dst"]] = KD.disc_post(src.unsqueeze(2), o["op"], o["bias"]).view(B, src.shape[1], 1)
+            n = len(MSD_LAYERS) - 1
+            feats = [bufs[j].permute(0, 2, 1) for j in range(n + 1)]
+            score = bufs[n].view(B, -1)
+            if keep:
+                state = dict(ops=ops, bufs=bufs, x=x2)
+        return score, feats, state
+
+    def _backward(self, state, gscore, gfeats, need_dx, need_params):
+        """(dx or None, the parameter gradients in named_parameters() order or Nones) from whichever of the nine output gradients
+        arrived: executes backward_plan()."""
+        ops, bufs, x2 = state["ops"], state["bufs"], state["x"]
+        n = len(MSD_LAYERS) - 1
+        B, T = x2.shape
+
+        def channel_last(g):
+            """a (B, C, L) gradient as contiguous (B, L, C): in place when it already is channel-last-strided, else one copy"""
+            if g is None:
+                return None
+            g = g.detach().float().permute(0, 2, 1)
+            return g if g.is_contiguous() else g.contiguous()
+
+        def flat(g):
+            return None if g is None else g.detach().float().reshape(B, -1).contiguous()
+
+        def four(t):
+            return None if t is None else t.unsqueeze(2)
+
+        gf = [channel_last(g) for g in gfeats[:n]]
+        out, parts, dpre, opT, dx = {}, None, None, None, None
+        with torch.no_grad():
+            for e in self.backward_plan(need_dx, need_params):
+                kind, layer = e["kind"], e["layer"]
+                o = ops[layer]
+                if kind == "post_bwd":
+                    dpre, wp, bp = KD.disc_post_bwd(four(bufs[e["src"]]), o["op"], dy1=flat(gscore), dy2=flat(gfeats[n]), add=four(gf[e["src"]]),
+                                                    slope=LRELU_SLOPE)
+                    dpre, parts = dpre.squeeze(2), (wp, bp)
+                elif kind == "wgrad":
+                    parts = KD.disc_wgrad(four(dpre), four(bufs[e["src"]]), e["stride"])
+                elif kind == "gconv_wgrad":
+                    parts = KM.msd_gconv_wgrad(dpre, bufs[e["src"]], e["groups"], e["stride"])
+                elif kind == "input_wgrad":
+                    parts = KM.msd_input_wgrad(dpre, x2)
+                elif kind == "finish":
+                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], o["v"], o["g"])
+                    parts = None
+                elif kind == "sn_finish":
+                    gw, _, gb = out[layer]
+                    out[layer] = (KM.msd_sn_finish(gw, o["v"], o["uv"][0], o["uv"][1], o["sigma"]), None, gb)
+                elif kind == "fold_bwd":
+                    opT = KV.hifigan_fold_bwd(0, o["w32"], torch.float32)
+                elif kind == "gfold_bwd":
+                    opT = KM.msd_fold_bwd(o["w32"], e["groups"])
+                elif kind == "dgrad":
+                    mask = bufs[e["mask"]]
+                    dpre = KD.disc_dgrad(four(dpre), opT, mask.shape[1], e["cin"], e["stride"], mask_src=four(mask), add=four(gf[e["mask"]]),
+                                         slope=LRELU_SLOPE).squeeze(2)
+                    opT = None
+                elif kind == "gconv_dgrad":
+                    mask = bufs[e["mask"]]
+                    dpre = KM.msd_gconv_dgrad(dpre, opT, mask.shape[1], e["cin"], e["groups"], e["stride"], mask_src=mask, add=gf[e["mask"]],
+                                              slope=LRELU_SLOPE)
+                    opT = None
+                else:
+                    dx = KM.msd_input_dgrad(dpre, o["w32"]).view(B, 1, T)
+        grads = []
+        for name, prm in self.named_parameters():
+            if not need_params:
+                grads.append(None)
+                continue
+            layer, leaf = name.rsplit(".", 1)
+            gw, gg, gb = out[layer]
+            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
+        return dx, grads
+
+    def forward(self, x):
+        self._check(x)
+        params = [prm for _, prm in self.named_parameters()]
+        if torch.is_grad_enabled() and (x.requires_grad or any(prm.requires_grad for prm in params)):
+            res = _ScaleFunction.apply(self, x, *params)
+            return res[0], list(res[1:])
+        score, feats, _ = self._run(x)
+        return score, feats
+
+
+class MultiScaleDiscriminator(nn.Module):
+    """HiFi-GAN multi-scale discriminator (reference urhythmic/vocoder.py:368-402): three ScaleDiscriminators, the first spectrally
+    normed, on x, pool(x) and pool(pool(x)).  x (B, 1, T) -> ([three scores], [three lists of eight features])."""
+
+    def __init__(self):
+        super().__init__()
+        self.discriminators = nn.ModuleList([ScaleDiscriminator(use_spectral_norm=True), ScaleDiscriminator(), ScaleDiscriminator()])
+        self.meanpools = nn.ModuleList([_MeanPool(), _MeanPool()])
+
+    def launch_plan(self):
+        plan = []
+        for i, d in enumerate(self.discriminators):
+            plan += ([dict(kind="pool", scale=i)] if i else []) + [dict(e, scale=i) for e in d.launch_plan()]
+        return plan
+
+    def backward_plan(self, need_dx=False, need_params=True):
+        plan = []
+        for i, d in enumerate(self.discriminators):
+            plan += [dict(e, scale=i) for e in d.backward_plan(need_dx, need_params)]
+        return plan + ([dict(kind="pool_bwd", scale=2), dict(kind="pool_bwd", scale=1)] if need_dx else [])
+
+    def forward(self, x):
+        scores, feats = [], []
+        for i, d in enumerate(self.discriminators):
+            if i:
+                d._check(x)
+                x = self.meanpools[i - 1](x)
+            score, feat = d(x)
+            scores.append(score)
+            feats.append(feat)
+        return scores, feats
+
+
+class HifiganDiscriminator(nn.Module):
+    """The reference's HifiganDiscriminator (urhythmic/vocoder.py:405-425): `mpd` + `msd`; forward returns the concatenated lists
+    (eight scores, eight lists of features)."""
+
+    def __init__(self):
+        super().__init__()
+        self.mpd = MultiPeriodDiscriminator()
+        self.msd = MultiScaleDiscriminator()
+
+    def launch_plan(self):
+        return self.mpd.launch_plan() + self.msd.launch_plan()
+
+    def backward_plan(self, need_dx=False, need_params=True):
+        return self.mpd.backward_plan(need_dx, need_params) + self.msd.backward_plan(need_dx, need_params)
+
+    def forward(self, x):
+        scores, feats = self.mpd(x)
+        scores_, feats_ = self.msd(x)
+        return scores + scores_, feats + feats_
