@@ -1084,6 +1084,48 @@ int s2svc_useg_search(int B, int Tmax, double gamma, const int32_t* lens, const 
 int s2svc_useg_stretch(int dtype, int B, int N, int C, const void* x, int64_t sb, int64_t st, int64_t sc, const int32_t* seg,
                        const int32_t* nsegs, int Smax, int Nmax, float scale, float* out, void* stream);
 
+/* ========================================================================================== */
+/* GAN losses of the HiFi-GAN fine-tuning loop (csrc/gan_loss.hip), table-driven: every tensor */
+/* (pair) of a call in ONE launch.  fp32, dense tensors walked in their physical storage.      */
+/* replaces: urhythmic/vocoder.py:428-465 (feature_loss, discriminator_loss, generator_loss    */
+/* and their autograd: a subtract / abs or square / mean / add chain per tensor)               */
+/* ========================================================================================== */
+/* elements per workgroup (8192) and entries per call (64), as the library states them */
+int s2svc_gan_loss_chunk(void);
+int s2svc_gan_loss_max(void);
+/* table (HOST, n rows of 6 int64): address of a, of b, of grad_a, of grad_b (b and the gradients may be 0), numel >= 1, kind
+   (0: mean((1 - a)^2), 1: mean(a^2), 2: mean(|a - b|)).  prefix (HOST, n + 1 int32): prefix[e] = the first workgroup of entry e,
+   prefix[e + 1] - prefix[e] = ceil(numel / chunk).  partials: prefix[n] doubles.  out: n + 1 floats, out[e] = fp32(the double sum of
+   entry e over its numel), out[n] = fp32(the double means added in ascending order).  Two launches (chunk sums, finish), no atomics.
+   replaces: urhythmic/vocoder.py:428-436 (feature_loss: kind 2 entries only) */
+int s2svc_gan_feature_loss(int n, const int64_t* table /* host */, const int32_t* prefix /* host */, double* partials, float* out, void* stream);
+/* One launch: t = fl(upstream[0] / numel) * sgn(a - b) with sgn(0) = 0; grad_a = t, grad_b = -t, each written where its address is not 0.
+   replaces: autograd of urhythmic/vocoder.py:428-436 */
+int s2svc_gan_feature_loss_bwd(int n, const int64_t* table /* host */, const int32_t* prefix /* host */, const float* upstream, void* stream);
+/* The least-squares losses, kind 0 and 1 entries only, same tables and outputs.
+   replaces: urhythmic/vocoder.py:439-465 (discriminator_loss, generator_loss) */
+int s2svc_gan_score_loss(int n, const int64_t* table /* host */, const int32_t* prefix /* host */, double* partials, float* out, void* stream);
+/* One launch: grad_a = fp32(2 upstream[0] (a - 1) / numel) (kind 0) or fp32(2 upstream[0] a / numel) (kind 1), computed in double.
+   replaces: autograd of urhythmic/vocoder.py:439-465 */
+int s2svc_gan_score_loss_bwd(int n, const int64_t* table /* host */, const int32_t* prefix /* host */, const float* upstream, void* stream);
+
+/* ========================================================================================== */
+/* Multi-tensor AdamW (csrc/adamw_multi.hip): up to 80 tensors per launch, their addresses as  */
+/* kernel arguments.  replaces: torch.optim.AdamW.step() as urhythmic_fine_tune_vocoder.py     */
+/* :99-110, :206, :222 runs it                                                                 */
+/* ========================================================================================== */
+/* tensors per call (80) and elements per workgroup (4096), as the library states them */
+int s2svc_adamw_multi_group(void);
+int s2svc_adamw_multi_chunk(void);
+/* table (HOST, n rows of 4 int64): address of the parameter, of its gradient, offset of its moments in exp_avg / exp_avg_sq (a multiple
+   of 4 elements, offset + numel <= moment_numel), numel.  prefix as above with the 4096-element chunk.  Per element, fp32:
+   p *= decay; m += one_minus_beta1 (g - m); v = beta2 v + one_minus_beta2 g g; p -= step_size[e] * m / (sqrt(v) / bc2_sqrt[e] + eps).
+   The host forms decay = 1 - lr wd, 1 - beta1 and 1 - beta2 in double (in fp32 the differences cancel) and rounds them once.
+   replaces: torch.optim.AdamW.step() over the same tensors */
+int s2svc_adamw_multi(int n, const int64_t* table /* host */, const int32_t* prefix /* host */, const float* step_size /* host */,
+                      const float* bc2_sqrt /* host */, int64_t moment_numel, float* exp_avg, float* exp_avg_sq, float decay,
+                      float one_minus_beta1, float beta2, float one_minus_beta2, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

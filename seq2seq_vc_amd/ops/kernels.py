@@ -1338,3 +1338,23 @@ def conv_in1_wgrad(x, dy, dw, db, accumulate, y=None):
     partial = torch.empty(chunks * O * 10, dtype=torch.float32, device=x.device)
     _lib.check(_lib.lib().s2svc_conv_in1_wgrad(dt(x), B, T, Fd, O, ptr(x), ptr(dy), ptr(y), ptr(dw), ptr(db), 1 if accumulate else 0,
                                                ptr(partial), chunks, stream()), "conv_in1_wgrad")
+
+
+def adamw_multi(rows, exp_avg, exp_avg_sq, decay, beta1, beta2, eps):
+    """One launch of csrc/adamw_multi.hip over rows [(parameter, gradient, moment offset, step_size, bc2_sqrt)] (at most 80): the
+    addresses travel as kernel arguments.  Contiguous fp32 GPU tensors; exp_avg / exp_avg_sq are the flat moment buffers."""
+    n = len(rows)
+    _need_cuda(exp_avg, exp_avg_sq, *[t for r in rows for t in r[:2]])
+    flat, numels = [], []
+    for p, g, off, _, _ in rows:
+        if p.dtype != torch.float32 or g.dtype != torch.float32 or not p.is_contiguous() or not g.is_contiguous() or p.shape != g.shape:
+            raise ValueError("adamw_multi: contiguous fp32 parameters and gradients of one shape")
+        flat += [p.data_ptr(), g.data_ptr(), int(off), p.numel()]
+        numels.append(p.numel())
+    chunk, prefix = int(_lib.lib().s2svc_adamw_multi_chunk()), [0]
+    for k in numels:
+        prefix.append(prefix[-1] + -(-k // chunk))
+    _lib.check(_lib.lib().s2svc_adamw_multi(n, (ctypes.c_int64 * len(flat))(*flat), (ctypes.c_int32 * len(prefix))(*prefix),
+                                            (ctypes.c_float * n)(*[r[3] for r in rows]), (ctypes.c_float * n)(*[r[4] for r in rows]),
+                                            exp_avg.numel(), ptr(exp_avg), ptr(exp_avg_sq), float(decay), 1.0 - float(beta1), float(beta2),
+                                            1.0 - float(beta2), float(eps), stream()), "adamw_multi")

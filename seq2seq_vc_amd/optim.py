@@ -11,6 +11,9 @@ transpose launch per step) so that data-gradient GEMMs read K-contiguous operand
 device tensor, so the optimiser step is hipGraph-capturable and needs no host synchronisation.  The
 flat gradient buffer is also what data-parallel training all-reduces (distributed.py): a handful of
 large RCCL collectives instead of one per tensor.
+
+MultiAdamW (end of this file) is the other kind: torch.optim.AdamW over the caller's own tensors, as a torch.optim.Optimizer with
+torch's state-dict layout, stepped by a few table-driven launches (csrc/adamw_multi.hip) -- the vocoder fine-tuning loop's optimiser.
 """
 import collections
 
@@ -377,3 +380,153 @@ class FlatAdam:
             self.exp_avg.copy_(sd["exp_avg"])
             self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.refresh_shadow()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# MultiAdamW: torch.optim.AdamW over the caller's own tensors, a few table-driven launches per step (csrc/adamw_multi.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+ADAMW_GROUP = 80        # tensors per launch; the library states the same number (adamw_multi_group)
+ADAMW_CHUNK = 4096      # elements per workgroup (adamw_multi_chunk)
+MOMENT_ALIGN = 4        # elements: every tensor's chunk of the flat moment buffers starts 16-byte aligned
+
+
+def plan_moments(numels, align=MOMENT_ALIGN):
+    """(offsets, total): tensor i owns [offsets[i], offsets[i] + numels[i]) of the two flat moment buffers, offsets multiples of
+    `align`; the gap up to the next offset belongs to nobody.  Pure host arithmetic."""
+    offsets, n = [], 0
+    for k in numels:
+        if k < 1:
+            raise ValueError("plan_moments: every tensor has at least one element")
+        offsets.append(n)
+        n = _round_up(n + int(k), align)
+    return offsets, n
+
+
+def adamw_table(numels, offsets, chunk=ADAMW_CHUNK):
+    """The index model of one launch over these tensors: the workgroup prefix table and, per workgroup, what it touches --
+    (tensor, [lo, hi) inside the tensor, vector elements, tail elements).  A workgroup walks whole groups of four from `lo` and then
+    the tensor's OWN tail: it never reaches past offsets[i] + numels[i], so it never touches the neighbour's chunk or the gap."""
+    prefix, work = [0], []
+    for i, k in enumerate(numels):
+        nch = -(-int(k) // chunk)
+        prefix.append(prefix[-1] + nch)
+        for c in range(nch):
+            lo, hi = c * chunk, min(int(k), (c + 1) * chunk)
+            work.append((i, lo, hi, (hi - lo) // 4 * 4, (hi - lo) % 4))
+    return prefix, work
+
+
+class MultiAdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW (decoupled weight decay, torch's formula, eps added after the sqrt(v) / sqrt(1 - beta2^t) division) with
+    every tensor of a step updated by a few table-driven HIP launches: the addresses of the parameters and of their -- every step
+    fresh -- gradients travel as kernel arguments in groups of 80, so a step is ceil(tensors with a gradient / 80) launches and
+    nothing else: 3 for the HiFi-GAN generator (234 tensors), 2 for the discriminator (154), no device table, no copy, no stream
+    stop, no per-tensor launch.  `exp_avg` / `exp_avg_sq` live in two flat buffers (`self.exp_avg`, `self.exp_avg_sq`), each
+    tensor's chunk 16-byte aligned; the state entries are views of them.
+
+    A torch.optim.Optimizer: lr schedulers accept it, `param_groups[i]["lr"]` is the live rate, read on the host at each step().
+    Parameters whose .grad is None are skipped and their step count does not advance, as in torch.  state_dict() /
+    load_state_dict() use torch.optim.AdamW's own layout (state[i] = {step, exp_avg, exp_avg_sq}, the same param_groups keys), so an
+    optimiser block of a reference checkpoint loads and ours loads into torch.optim.AdamW; state_dict() holds copies, and
+    load_state_dict() copies into the flat buffers without rebinding them.  fp32 parameters on the GPU only (construction and the
+    state-dict layout work on CPU tensors; step() there raises)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("MultiAdamW: lr, eps, weight_decay >= 0 and 0 <= beta < 1")
+        params = list(params)
+        # torch's own defaults dict for these arguments: the param_groups keys of whatever torch release is installed
+        defaults = dict(torch.optim.AdamW([torch.nn.Parameter(torch.zeros(1))], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay).defaults)
+        super().__init__(params, defaults)
+        flat = [p for g in self.param_groups for p in g["params"]]
+        for p in flat:
+            if p.dtype != torch.float32:
+                raise TypeError("MultiAdamW: float32 parameters")
+            if not p.is_contiguous():
+                raise ValueError("MultiAdamW: contiguous parameters")
+        if len({p.device for p in flat}) != 1:
+            raise ValueError("MultiAdamW: all parameters on one device")
+        self._flat = flat
+        self.offsets, self.numel = plan_moments([p.numel() for p in flat])
+        dev = flat[0].device
+        self.exp_avg = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(self.numel, dtype=torch.float32, device=dev)
+        self._offset_of = {id(p): o for p, o in zip(flat, self.offsets)}
+        # the step counts of all tensors in ONE host tensor, state[p]["step"] a 0-dim view of it: one vector increment and one
+        # tolist() per step (a `+= 1` and a float() per tensor were 70 % of step()'s host time over 154 tensors)
+        self._steps = torch.zeros(len(flat), dtype=torch.float32)
+        self._index_of = {id(p): i for i, p in enumerate(flat)}
+
+    def launches_per_step(self, tensors=None):
+        """Library launches of one step() over `tensors` tensors with a gradient (default: all)."""
+        return -(-(len(self._flat) if tensors is None else tensors) // ADAMW_GROUP)
+
+    def _views(self, p):
+        o, k = self._offset_of[id(p)], p.numel()
+        return self.exp_avg[o:o + k].view(p.shape), self.exp_avg_sq[o:o + k].view(p.shape)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("maximize"):
+                raise NotImplementedError("MultiAdamW: amsgrad / maximize are not implemented")
+            lr, (beta1, beta2), eps, wd = float(group["lr"]), group["betas"], float(group["eps"]), float(group["weight_decay"])
+            live = []
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not p.is_cuda:
+                    raise RuntimeError("MultiAdamW needs GPU parameters (there is no CPU path)")
+                g = p.grad
+                if g.is_sparse or g.dtype != torch.float32:
+                    raise TypeError("MultiAdamW: dense float32 gradients")
+                if not g.is_contiguous():
+                    g = g.contiguous()
+                st = self.state[p]
+                if not st:
+                    st["step"] = self._steps[self._index_of[id(p)]]
+                    st["exp_avg"], st["exp_avg_sq"] = self._views(p)
+                live.append((p, g, self._index_of[id(p)]))
+            if len(live) == len(self._flat):
+                self._steps += 1
+            elif live:
+                self._steps[[i for _, _, i in live]] += 1
+            counts, corr, rows = self._steps.tolist(), {}, []
+            for p, g, i in live:
+                t = counts[i]
+                if t not in corr:
+                    corr[t] = (lr / (1.0 - beta1 ** t), (1.0 - beta2 ** t) ** 0.5)
+                rows.append((p, g) + corr[t])
+            for i in range(0, len(rows), ADAMW_GROUP):
+                K.adamw_multi([(p, g, self._offset_of[id(p)], ss, bs) for p, g, ss, bs in rows[i:i + ADAMW_GROUP]], self.exp_avg,
+                              self.exp_avg_sq, 1.0 - lr * wd, beta1, beta2, eps)
+        return loss
+
+    def state_dict(self):
+        """torch.optim.AdamW's layout; the moments and step counts are copies (a checkpoint does not move with later steps)."""
+        sd = super().state_dict()
+        sd["state"] = {i: {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in st.items()} for i, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Accepts torch.optim.AdamW state dicts (and this class's own): the moments are copied INTO the flat buffers, which stay
+        where they are; parameters without an entry go back to zero moments and no state."""
+        super().load_state_dict(state_dict)
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        self._steps.zero_()
+        for p in self._flat:
+            st = self.state.get(p)
+            if not st:
+                continue
+            m, v = self._views(p)
+            m.copy_(st["exp_avg"])
+            v.copy_(st["exp_avg_sq"])
+            st["exp_avg"], st["exp_avg_sq"] = m, v
+            i = self._index_of[id(p)]
+            self._steps[i] = float(st["step"])
+            st["step"] = self._steps[i]

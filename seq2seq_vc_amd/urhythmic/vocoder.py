@@ -6,8 +6,9 @@ ScaleDiscriminator / MultiScaleDiscriminator (:330-402) and HifiganDiscriminator
 `state_dict` keys and shapes (`discriminators.{i}.convs.{j}.{bias,weight_g,weight_v}`, `conv_post.*`, weights (O, C, k, 1) in the
 period discriminators and (O, C / groups, k) in the scale discriminators; the spectrally normed first scale holds `bias, weight_orig`
 and the buffers `weight_u, weight_v`) and the call `forward(x (B, 1, T)) -> (scores, feats)`; a reference checkpoint of the whole
-discriminator, or its `mpd.*` / `msd.*` subtree, loads as it is.  The three loss functions and the optimiser stay the caller's stock
-torch code.
+discriminator, or its `mpd.*` / `msd.*` subtree, loads as it is.  The three loss functions of the reference (:428-465) are at the end
+of this file, one autograd node and one table-driven launch sequence each (csrc/gan_loss.hip); the optimiser is optim.MultiAdamW and
+the whole loop body is urhythmic/fine_tune.py.
 
 A ScaleDiscriminator call is ONE autograd node as well (inputs x and its 16 or 24 parameters, outputs the score and eight features);
 the average pool between the scales is a small node of its own.  The spectrally normed scale runs one power iteration per call in
@@ -27,6 +28,7 @@ import torch
 from torch import nn
 
 from ..ops import kernels_disc as KD
+from ..ops import kernels_ganloss as KG
 from ..ops import kernels_msd as KM
 from ..ops import kernels_vocoder as KV
 
@@ -597,3 +599,117 @@ class HifiganDiscriminator(nn.Module):
         scores, feats = self.mpd(x)
         scores_, feats_ = self.msd(x)
         return scores + scores_, feats + feats_
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the three losses (csrc/gan_loss.hip)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _loss_inputs(name, tensors):
+    """The checks of the discriminators' `_check`, on every tensor of a loss call."""
+    if not tensors:
+        raise ValueError(f"{name}: no tensors")
+    for t in tensors:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: tensors expected, got {type(t).__name__}")
+        if t.dtype in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"{name} runs in fp32 only, as the discriminators do (DESIGN.md section 8)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: float32 tensors")
+        if not t.is_cuda:
+            raise RuntimeError(f"{name} needs GPU tensors (there is no CPU path)")
+
+
+class _FeatureLossFunction(torch.autograd.Function):
+    """feature_loss as ONE autograd node.  launch plan: forward 2 library launches (chunk sums of every pair, finish), backward 1
+    (sign and fl(upstream / numel) recomputed from the saved inputs: nothing is stored between the passes but the inputs)."""
+
+    @staticmethod
+    def forward(ctx, n, *tensors):
+        pairs = []
+        for r, g in zip(tensors[:n], tensors[n:]):
+            r, g = r.detach(), g.detach()
+            if r.shape != g.shape:
+                raise ValueError(f"feature_loss: a pair of shapes {tuple(r.shape)} and {tuple(g.shape)}")
+            if not (KG.dense_like(r) and KG.same_layout(r, g)):
+                r, g = r.contiguous(), g.contiguous()
+            pairs.append((r, g))
+        out = KG.feature_loss_fwd(pairs)
+        ctx.pairs = pairs
+        ctx.save_for_backward(*tensors)          # the version check of the inputs
+        means = out[:n]
+        ctx.mark_non_differentiable(means)
+        return out[n], means
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_means):
+        ctx.saved_tensors
+        n = len(ctx.pairs)
+        need = ctx.needs_input_grad[1:]
+        ga, gb = KG.feature_loss_bwd(ctx.pairs, g_loss.detach().float().reshape(1), need[:n], need[n:])
+        return (None,) + tuple(ga) + tuple(gb)
+
+
+def feature_loss(features_real, features_generated):
+    """The reference's feature_loss (urhythmic/vocoder.py:428-436): the sum over all feature pairs of mean(|real - generated|), one
+    autograd node, 2 launches forward and 1 backward for all (54) pairs.  The pairs are walked in their physical storage: the
+    discriminators' features are permuted views of dense channel-last buffers, both tensors of a pair equally strided, and the gradient
+    comes back in the same layout, which the discriminators' backward reads in place.  A pair that is not dense and equally strided
+    gets one contiguous copy of each tensor first.  The gradient is fl(upstream / numel) * sgn(real - generated) for `real` and its
+    negation for `generated` (stock torch's fp32 values, signed zeros included), each computed only when that side requires grad."""
+    real = [t for fl in features_real for t in fl]
+    gen = [t for fl in features_generated for t in fl]
+    if len(real) != len(gen):
+        raise ValueError(f"feature_loss: {len(real)} real features, {len(gen)} generated ones")
+    _loss_inputs("feature_loss", real + gen)
+    return _FeatureLossFunction.apply(len(real), *real, *gen)[0]
+
+
+class _ScoreLossFunction(torch.autograd.Function):
+    """The least-squares losses over a list of score tensors as ONE autograd node.  launch plan: forward 2 library launches, backward 1."""
+
+    @staticmethod
+    def forward(ctx, kinds, *tensors):
+        entries = []
+        for x, kind in zip(tensors, kinds):
+            x = x.detach()
+            entries.append((x if KG.dense_like(x) else x.contiguous(), kind))
+        out = KG.score_loss_fwd(entries)
+        ctx.entries = entries
+        ctx.save_for_backward(*tensors)
+        means = out[:len(entries)]
+        ctx.mark_non_differentiable(means)
+        return out[len(entries)], means
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_means):
+        ctx.saved_tensors
+        return (None,) + tuple(KG.score_loss_bwd(ctx.entries, g_loss.detach().float().reshape(1), ctx.needs_input_grad[1:]))
+
+
+def discriminator_loss(real, generated, detail=True):
+    """The reference's discriminator_loss (urhythmic/vocoder.py:439-452): sum over the pairs of mean((1 - r)^2) + mean(g^2) ->
+    (loss, real_losses, generated_losses).  One autograd node, 2 launches forward, 1 backward.  The two lists are Python floats as in
+    the reference, read with ONE device-to-host copy (the reference reads 16 times); detail=False returns empty lists and never
+    touches the host."""
+    real, generated = list(real), list(generated)
+    if len(real) != len(generated):
+        raise ValueError(f"discriminator_loss: {len(real)} real scores, {len(generated)} generated ones")
+    _loss_inputs("discriminator_loss", real + generated)
+    n = len(real)
+    loss, means = _ScoreLossFunction.apply((KG.KIND_ONE_MINUS_SQ,) * n + (KG.KIND_SQ,) * n, *real, *generated)
+    if not detail:
+        return loss, [], []
+    host = means.tolist()
+    return loss, host[:n], host[n:]
+
+
+def generator_loss(discriminator_outputs):
+    """The reference's generator_loss (urhythmic/vocoder.py:455-465): sum of mean((1 - x)^2) -> (loss, [the per-score losses]).  One
+    autograd node; the per-score losses are 0-dim views of one device vector and, unlike the reference's, carry no gradient (the loop
+    logs them)."""
+    outputs = list(discriminator_outputs)
+    _loss_inputs("generator_loss", outputs)
+    loss, means = _ScoreLossFunction.apply((KG.KIND_ONE_MINUS_SQ,) * len(outputs), *outputs)
+    return loss, list(means.unbind(0))
