@@ -1126,6 +1126,44 @@ int s2svc_adamw_multi(int n, const int64_t* table /* host */, const int32_t* pre
                       const float* bc2_sqrt /* host */, int64_t moment_numel, float* exp_avg, float* exp_avg_sq, float decay,
                       float one_minus_beta1, float beta2, float one_minus_beta2, float eps, void* stream);
 
+/* ========================================================================================== */
+/* Attention forward without the map (csrc/attn_flash.hip): online softmax over key tiles.     */
+/* Inference only: no dropout, no backward, nothing but ctx is written.                        */
+/* replaces: the scaled-dot-product core of torch.nn.MultiheadAttention inside the              */
+/* nn.TransformerEncoderLayer stack of the HuBERT-Soft content encoder (urhythmic/hubert.py)   */
+/* ========================================================================================== */
+/* 1 if _fwd takes the problem: dtype 0 / 1, dk = 64, every row stride a whole number of 16-byte vectors and >= 64 */
+int s2svc_attn_flash_supported(int dtype, int dk, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo);
+/* q element (b, t, h, d) at b*qbs + t*ldq + h*dk + d (t < T1), k and v alike (t < T2), ctx alike (t < T1): slices of one packed
+   (B, T, 3 D) projection are such views.  16-byte aligned pointers and batch strides.  klen (B) int32 or NULL (= T2 everywhere): keys
+   t >= min(klen[b], T2) are never read; query rows t >= klen[b], and every row of an utterance with klen[b] <= 0, are written as +0.
+   ctx = softmax(scale * q k^T) v per (b, h), fp32 accumulation; the result of one (b, h, 64-row query tile) depends on its own
+   rows and keys only -- not on B and not on T1 / T2 beyond klen[b]. */
+int s2svc_attn_flash_fwd(int dtype, int B, int H, int T1, int T2, int dk, const void* q, int64_t qbs, int64_t ldq, const void* k,
+                         int64_t kbs, int64_t ldk, const void* v, int64_t vbs, int64_t ldv, const int32_t* klen, float scale, void* ctx,
+                         int64_t obs, int64_t ldo, void* stream);
+
+/* ========================================================================================== */
+/* HuBERT-Soft content encoder (csrc/hubert.hip): front-end layer 0 and the unit log-probs.    */
+/* replaces: bshall/hubert FeatureExtractor.conv0 / norm0 / gelu, Hubert.logits, and the        */
+/* log_softmax of urhythmic/model.py:33-35                                                     */
+/* ========================================================================================== */
+/* Conv1d(1, 512, 10, stride 5, no bias) -> GroupNorm(512, 512) -> exact GELU over wav (B, Nmax) fp32, row b being its first lens[b]
+   samples padded by `pad` zeros on both sides (index arithmetic; HubertSoft.units: 40): L0_b = (lens[b] + 2 pad - 10) / 5 + 1 frames.  w (512, 10) fp32.
+   _stats: per (row, channel) sum y and sum y^2 over the row's own frames in double, 32 ordered chunk pairs ws[b][32][2][512]
+           (_ws_bytes(B) bytes); no atomics; samples at or beyond lens[b] are never read.
+   _apply: adds the pairs in chunk order, recomputes the product, normalises with the biased variance and eps, applies gamma / beta (512)
+           and the GELU, writes out (B, L0max, 512) in dtype 0 / 1; frames at or beyond L0_b are +0. */
+int64_t s2svc_hubert_conv0_ws_bytes(int B);
+int s2svc_hubert_conv0_stats(int B, int Nmax, int pad, const float* wav, const int32_t* lens, const float* w, double* ws, void* stream);
+int s2svc_hubert_conv0_apply(int dtype, int B, int Nmax, int pad, int L0max, const float* wav, const int32_t* lens, const float* w,
+                             const float* gamma, const float* beta, float eps, const double* ws, void* out, void* stream);
+/* out (B * L, K) fp32 = log_softmax_k(cosine_similarity(units[row], emb[k]) / 0.1) (log_softmax = 0: the quotient itself), units (B * L, 256) in dtype 0 / 1, emb (K <= 256,
+   256) fp32, cosine = x.e / (max(|x|, 1e-8) * max(|e|, 1e-8)); fp32 arithmetic, one wavefront per row.  lens (B) int32 or NULL: rows
+   (b, t >= lens[b]) are written as +0. */
+int s2svc_hubert_logits(int dtype, int B, int L, int K, int log_softmax, const void* units, const int32_t* lens, const float* emb, float* out,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

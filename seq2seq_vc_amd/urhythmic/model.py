@@ -1,11 +1,41 @@
 """Urhythmic (fine-grained) conversion inside the package (reference urhythmic/model.py): segmenter -> rhythm model -> time stretcher
--> vocoder, single and batched."""
+-> vocoder, single and batched; and the step before it, encode / encode_batch: waveform -> soft units and unit log-probs."""
 import torch
 from torch import nn
 
+from ..ops import kernels_hubert as KH
+from .hubert import HubertSoft, _host_lens, _inference_only, _wav2
 from .rhythm_model import RhythmModelFineGrained
 from .segmenter import Segmenter, _device_log_probs
 from .stretcher import TimeStretcherFineGrained
+
+
+def _need_hubert(hubert):
+    if not isinstance(hubert, HubertSoft):
+        raise TypeError("encode: a seq2seq_vc_amd.urhythmic.hubert.HubertSoft expected (load the hub checkpoint's state_dict into one: "
+                        "INTEGRATION.md); there is no path through another implementation")
+
+
+@torch.inference_mode()
+def encode(hubert: HubertSoft, wav: torch.Tensor):
+    """Encode a waveform into soft speech units and the log probabilities of the associated discrete units (reference
+    urhythmic/model.py:22-36).  wav (B, 1, T), every row T samples -> units (B, D, N) fp32, log_probs (B, N, K) fp32."""
+    _need_hubert(hubert)
+    units = hubert.units(wav)
+    log_probs = KH.hubert_logits(units, hubert.label_embedding.weight)
+    return units.transpose(1, 2), log_probs
+
+
+@torch.inference_mode()
+def encode_batch(hubert: HubertSoft, wavs: torch.Tensor, lens):
+    """wavs (B, 1, Tmax), lens (B) samples of every row (list or CPU tensor) -> units (B, D, Nmax), log_probs (B, Nmax, K), frame_lens (B)
+    int32 on the CPU: what UrhythmicFine.convert_batch takes.  Every row is computed from its own samples only; units and log_probs are
+    zero beyond a row's frames."""
+    _need_hubert(hubert)
+    _inference_only(hubert, wavs, grad_ok=True)
+    units, frame_lens, frame_lens_dev = hubert._units(_wav2(wavs), _host_lens(lens), True)
+    log_probs = KH.hubert_logits(units, hubert.label_embedding.weight, lens=frame_lens_dev)
+    return units.transpose(1, 2), log_probs, torch.tensor(frame_lens, dtype=torch.int32)
 
 
 class UrhythmicFine(nn.Module):
