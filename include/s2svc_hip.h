@@ -1077,6 +1077,21 @@ int s2svc_useg_spans(int B, int Tmax, int K, const float* log_probs, const int32
 int s2svc_useg_search(int B, int Tmax, double gamma, const int32_t* lens, const void* ws, const int32_t* labels, int32_t* codes,
                       int32_t* boundaries, int32_t* nseg, float* alpha, int32_t* P, int32_t* clusters, int32_t* cboundaries,
                       int32_t* ncl, void* stream);
+/* The stretch plan on the device: the merged clusters of s2svc_useg_search and the rhythm model's duration table -> the seg table
+   s2svc_useg_stretch reads (Smax = Tmax).  table (n_clusters, Lmax + 1) int32: target frames of a segment of n frames of cluster c;
+   INT32_MIN marks a length the rhythm model cannot map.  Per row (ncl clamped to [0, Tmax]): a segment is kept unless its cluster is
+   silence_cluster and it has at most short_silence frames; a kept segment whose target is <= 0 is dropped; the survivors are written
+   in order as (cboundaries[i], n, target, exclusive prefix sum of the targets), every seg row from nsegs[b] to Tmax is zero.
+   status[b]: 0 ok; 1 a kept segment met INT32_MIN; 2 malformed input (n < 1, n > Lmax, cluster outside [0, n_clusters), a boundary
+   outside [0, Tmax]); 3 the targets add up to more than INT32_MAX (added in 64 bits).  A row whose status is not 0 has nsegs = totals
+   = 0 and an all-zero seg.  Nothing beyond ncl[b] is read and no index leaves its array whatever the tables hold.  One wave per row,
+   one launch, no atomics, no workspace.
+   replaces: the host work between the two (urhythmic/rhythm_model.py:150-161, two scipy calls per segment, and the two filters of
+   urhythmic/stretcher.py:41-53) */
+int s2svc_useg_plan(int B, int Tmax, int n_clusters, int Lmax, const int32_t* clusters /* (B, Tmax) */,
+                    const int32_t* cboundaries /* (B, Tmax + 1) */, const int32_t* ncl /* (B) */,
+                    const int32_t* table /* (n_clusters, Lmax + 1) */, int silence_cluster, int short_silence,
+                    int32_t* seg /* (B, Tmax, 4) */, int32_t* nsegs, int32_t* totals, int32_t* status /* (B) each */, void* stream);
 /* Segment-wise linear resampling (F.interpolate(mode="linear", align_corners=False) of every segment on its own, concatenated).
    x element (b, t, c) at b*sb + t*st + c*sc, t < N, dtype 0 / 1; seg (B, Smax, 4) int32 = (source start, source length, target length,
    exclusive prefix sum of the target lengths), nsegs (B); target lengths are positive.  out (B, Nmax, C) fp32, zero past the row's

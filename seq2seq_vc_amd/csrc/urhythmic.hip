@@ -1,5 +1,6 @@
-// Urhythmic on the GPU: the segmentation search (span scores, dynamic programme, backtrack, cluster merge) and the segment-wise linear
-// resampling of the time stretcher.
+// Urhythmic on the GPU: the segmentation search (span scores, dynamic programme, backtrack, cluster merge), the stretch plan (merged
+// clusters + the rhythm model's duration table -> the stretcher's segment table) and the segment-wise linear resampling of the time
+// stretcher.
 //
 // reference: seq2seq_vc/urhythmic/segmenter.py:138-191 (_segment, numba-JIT on the host over a dense (T, T, K) fp32 table; _backtrack;
 // cluster_merge) and seq2seq_vc/urhythmic/stretcher.py:23-71 (F.interpolate per segment + torch.cat).
@@ -301,6 +302,92 @@ __global__ __launch_bounds__(256) void useg_stretch_kernel(int N, int C, const T
   }
 }
 
+// The stretch plan: the search's merged clusters of one row -> the stretcher's segment table, through the rhythm model's duration
+// table.  One wave per row, a lane per segment, chunks of 64.  Two passes over the row: the first only judges it (malformed input,
+// an unmapped length, the 64-bit total of the targets), the second writes -- so a row that is refused is written as zeros once and no
+// store depends on the order of another.  Every index is checked before it is used: nothing is assumed about what the tables hold.
+constexpr int32_t USEG_UNMAPPED = INT32_MIN;
+
+struct PlanItem { int start, n, target; bool bad, unmapped; };
+
+__device__ __forceinline__ PlanItem useg_plan_item(int i, int ncl, int Tmax, int n_clusters, int Lmax, const int32_t* __restrict__ cl,
+                                                   const int32_t* __restrict__ cb, const int32_t* __restrict__ table, int silence_cluster,
+                                                   int short_silence) {
+  PlanItem it = {0, 0, 0, false, false};
+  if (i >= ncl) return it;                                       // i + 1 <= ncl <= Tmax: cb[i + 1] exists
+  const int lo = cb[i], hi = cb[i + 1], c = cl[i];
+  if (lo < 0 || lo > Tmax || hi < 0 || hi > Tmax || hi - lo < 1 || hi - lo > Lmax || c < 0 || c >= n_clusters) {
+    it.bad = true;
+    return it;
+  }
+  it.start = lo;
+  it.n = hi - lo;
+  if (c == silence_cluster && it.n <= short_silence) return it;  // a short silence: dropped before the durations pair up
+  const int32_t t = table[(int64_t)c * (Lmax + 1) + it.n];
+  it.unmapped = t == USEG_UNMAPPED;
+  it.target = t > 0 ? t : 0;                                     // a target <= 0 drops its segment
+  return it;
+}
+
+__global__ __launch_bounds__(64) void useg_plan_kernel(int Tmax, int n_clusters, int Lmax, const int32_t* __restrict__ clusters,
+                                                       const int32_t* __restrict__ cboundaries, const int32_t* __restrict__ ncls,
+                                                       const int32_t* __restrict__ table, int silence_cluster, int short_silence,
+                                                       int32_t* __restrict__ seg, int32_t* __restrict__ nsegs, int32_t* __restrict__ totals,
+                                                       int32_t* __restrict__ status) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int32_t* cl = clusters + (int64_t)b * Tmax;
+  const int32_t* cb = cboundaries + (int64_t)b * (Tmax + 1);
+  int32_t* sg = seg + (int64_t)b * Tmax * 4;
+  int ncl = ncls[b];
+  ncl = ncl < 0 ? 0 : (ncl > Tmax ? Tmax : ncl);
+
+  bool bad = false, unmapped = false;
+  int64_t sum = 0;
+  for (int i0 = 0; i0 < ncl; i0 += 64) {
+    const PlanItem it = useg_plan_item(i0 + lane, ncl, Tmax, n_clusters, Lmax, cl, cb, table, silence_cluster, short_silence);
+    bad |= it.bad;
+    unmapped |= it.unmapped;
+    sum += it.target;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  int st = 0;
+  if (__ballot(bad)) st = 2;
+  else if (__ballot(unmapped)) st = 1;
+  else if (sum > (int64_t)INT32_MAX) st = 3;
+
+  int base = 0;
+  if (st == 0) {                                                 // wave-uniform; every partial sum below is <= sum <= INT32_MAX
+    int run = 0;
+    for (int i0 = 0; i0 < ncl; i0 += 64) {
+      const PlanItem it = useg_plan_item(i0 + lane, ncl, Tmax, n_clusters, Lmax, cl, cb, table, silence_cluster, short_silence);
+      const bool keep = it.target > 0;
+      const uint64_t m = __ballot(keep);
+      int incl = it.target;                                      // inclusive prefix sum of the chunk's targets
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      if (keep) {
+        const int pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));      // pos <= i0 + lane < Tmax
+        sg[pos * 4] = it.start;
+        sg[pos * 4 + 1] = it.n;
+        sg[pos * 4 + 2] = it.target;
+        sg[pos * 4 + 3] = run + incl - it.target;
+      }
+      base += __builtin_popcountll(m);
+      run += __shfl(incl, 63, 64);
+    }
+  }
+  for (int i = base * 4 + lane; i < Tmax * 4; i += 64) sg[i] = 0;
+  if (lane == 0) {
+    nsegs[b] = base;
+    totals[b] = st == 0 ? (int32_t)sum : 0;
+    status[b] = st;
+  }
+}
+
 }  // namespace
 
 extern "C" int64_t s2svc_useg_ws_bytes(int B, int Tmax, int K) {
@@ -348,6 +435,20 @@ extern "C" int s2svc_useg_search(int B, int Tmax, double gamma, const int32_t* l
                      (const uint16_t*)useg_kx(const_cast<void*>(ws), B, Tmax), labels, codes, boundaries, nseg, alpha, P, clusters,
                      cboundaries, ncl);
   S2S_CHECK_LAUNCH("useg_search_kernel");
+  return 0;
+}
+
+extern "C" int s2svc_useg_plan(int B, int Tmax, int n_clusters, int Lmax, const int32_t* clusters, const int32_t* cboundaries,
+                               const int32_t* ncl, const int32_t* table, int silence_cluster, int short_silence, int32_t* seg,
+                               int32_t* nsegs, int32_t* totals, int32_t* status, void* stream) {
+  S2S_REQUIRE(B >= 0 && Tmax > 0 && n_clusters > 0 && Lmax >= 0, "useg_plan: bad shape");
+  S2S_REQUIRE(Tmax <= USEG_MAX_T, "useg_plan: Tmax > 4096 not supported");
+  S2S_REQUIRE(B <= 65535, "useg_plan: B > 65535 not supported");
+  S2S_REQUIRE(clusters && cboundaries && ncl && table && seg && nsegs && totals && status, "useg_plan: null argument");
+  if (B == 0) return 0;
+  hipLaunchKernelGGL(useg_plan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, Tmax, n_clusters, Lmax, clusters, cboundaries, ncl, table,
+                     silence_cluster, short_silence, seg, nsegs, totals, status);
+  S2S_CHECK_LAUNCH("useg_plan_kernel");
   return 0;
 }
 

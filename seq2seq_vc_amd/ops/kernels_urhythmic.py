@@ -1,5 +1,5 @@
-"""Launchers of the urhythmic kernels (csrc/urhythmic.hip; C ABI in include/s2svc_hip.h): segmentation search and segment-wise linear
-resampling.  Non-differentiable, GPU tensors only; every argument is device-resident, so no launcher waits for the device."""
+"""Launchers of the urhythmic kernels (csrc/urhythmic.hip; C ABI in include/s2svc_hip.h): segmentation search, stretch plan and
+segment-wise linear resampling.  Non-differentiable, GPU tensors only; every argument is device-resident, so no launcher waits for the device."""
 import torch
 
 from .. import _lib
@@ -95,5 +95,44 @@ def useg_stretch(units, seg, nsegs, n_out, channel_dim=1, scale=0.0):
     st, sc = units.stride(3 - channel_dim), units.stride(channel_dim)
     _lib.check(_lib.lib().s2svc_useg_stretch(0 if units.dtype == torch.float32 else 1, B, N, C, ptr(units), units.stride(0), st, sc, ptr(seg),
                                              ptr(nsegs), seg.shape[1], int(n_out), float(scale), ptr(out), stream()), "useg_stretch")
+    _count()
+    return out
+
+
+def check_plan_args(clusters, cboundaries, ncl, table):
+    """Shape / dtype / limit checks of useg_plan (ValueError), before any device work."""
+    if clusters.dim() != 2 or clusters.dtype != torch.int32 or not clusters.is_contiguous():
+        raise ValueError(f"clusters: a contiguous int32 (B, Tmax) table expected, got {clusters.dtype} {tuple(clusters.shape)}")
+    B, Tmax = clusters.shape
+    if not 1 <= Tmax <= MAX_T:
+        raise ValueError(f"the stretch plan supports 1 .. {MAX_T} frames, got Tmax = {Tmax}")
+    if B > 65535:
+        raise ValueError(f"the stretch plan supports up to 65535 rows, got B = {B}")
+    if cboundaries.dim() != 2 or tuple(cboundaries.shape) != (B, Tmax + 1):
+        raise ValueError(f"cboundaries: (B, Tmax + 1) = ({B}, {Tmax + 1}) expected, got {tuple(cboundaries.shape)}")
+    _i32c(cboundaries, B * (Tmax + 1), "cboundaries")
+    _i32c(ncl, B, "ncl")
+    if table.dim() != 2 or table.shape[0] < 1 or table.shape[1] < 1 or table.dtype != torch.int32 or not table.is_contiguous():
+        raise ValueError(f"table: a contiguous int32 (n_clusters, Lmax + 1) duration table expected, got {table.dtype} {tuple(table.shape)}")
+    return B, Tmax
+
+
+def useg_plan(clusters, cboundaries, ncl, table, silence_cluster, short_silence=3):
+    """The stretch plan on the device.  clusters (B, Tmax), cboundaries (B, Tmax + 1), ncl (B): the merged clusters of useg_segment;
+    table (n_clusters, Lmax + 1) int32: RhythmModelFineGrained.duration_table -> dict of device tensors: seg (B, Tmax, 4), what
+    useg_stretch reads with Smax = Tmax, and nsegs, totals (output frames), status (0 ok, 1 unmapped length, 2 malformed input,
+    3 total above INT32_MAX), each (B) and a view of the one (3, B) int32 buffer `packed` (one device-to-host copy fetches all three).
+    A row whose status is not 0 has nsegs = totals = 0.  One launch whatever B is."""
+    B, Tmax = check_plan_args(clusters, cboundaries, ncl, table)
+    _need_cuda(clusters, cboundaries, ncl, table)
+    dev = clusters.device
+    seg = torch.empty(B, Tmax, 4, dtype=torch.int32, device=dev)
+    packed = torch.empty(3, B, dtype=torch.int32, device=dev)
+    out = dict(seg=seg, nsegs=packed[0], totals=packed[1], status=packed[2], packed=packed)
+    if B == 0:
+        return out
+    _lib.check(_lib.lib().s2svc_useg_plan(B, Tmax, table.shape[0], table.shape[1] - 1, ptr(clusters), ptr(cboundaries), ptr(ncl), ptr(table),
+                                          int(silence_cluster), int(short_silence), ptr(seg), ptr(out["nsegs"]), ptr(out["totals"]),
+                                          ptr(out["status"]), stream()), "useg_plan")
     _count()
     return out

@@ -106,6 +106,16 @@ class Segmenter:
             self._labels[key] = torch.from_numpy(np.asarray(self.clustering.labels_).astype(np.int32)).to(device)
         return self._labels[key]
 
+    def segment_tables(self, log_probs, lens):
+        """log_probs (B, Tmax, K) fp32 and lens (B) int32 on the device -> the device tensors of ops.kernels_urhythmic.useg_segment with
+        the clustering's labels (clusters, cboundaries, ncl, ..).  Two launches whatever B is, and no host read: what
+        ops.kernels_urhythmic.useg_plan takes."""
+        KU.check_segment_args(log_probs, lens)
+        labels = np.asarray(self.clustering.labels_)
+        if labels.shape != (log_probs.shape[2],):
+            raise ValueError(f"the clustering knows {labels.shape[0]} units, log_probs has {log_probs.shape[2]}")
+        return KU.useg_segment(log_probs, lens, self.gamma, labels=self._device_labels(log_probs.device))
+
     def segment_batch(self, log_probs, lens, want_tables=False):
         """log_probs (B, Tmax, K) fp32 and lens (B) int32 on the device -> (tables, rows).  tables: the device tensors of
         ops.kernels_urhythmic.useg_segment (clusters, cboundaries, ncl, codes, boundaries, nseg, ..); rows: per utterance

@@ -1,6 +1,7 @@
 """Urhythmic time stretchers (reference urhythmic/stretcher.py) on the resampling kernel of csrc/urhythmic.hip: every segment is
 linearly resampled to its target duration on its own (F.interpolate(mode="linear"), no neighbour across a boundary) and the pieces
-stand side by side.  One launch for a whole batch; the bookkeeping (which segments survive, where they land) is host code."""
+stand side by side.  One launch for a whole batch; the bookkeeping (which segments survive, where they land) is host code
+(stretch_batch) or the plan kernel's (stretch_planned: ops.kernels_urhythmic.useg_plan, the same two filters on the device)."""
 import math
 
 import numpy as np
@@ -56,6 +57,16 @@ class TimeStretcherFineGrained:
                 raise ValueError("stretch_batch: a segment lies outside the units")
         seg, nsegs, totals = segment_table(plans, units.device)
         return KU.useg_stretch(units, seg, nsegs, max(totals, default=0), channel_dim=1), totals
+
+    def stretch_planned(self, units, plan, n_out):
+        """units (B, D, Tmax) as for stretch_batch; plan: what ops.kernels_urhythmic.useg_plan returned for the segmentation of these
+        units (its segment table stays on the device); n_out: the largest of the plan's totals -> stretched (B, n_out, D) fp32
+        channel-last, zero past each row's own frames.  One launch whatever B is."""
+        _check_units(units)
+        seg = plan["seg"]
+        if seg.dim() != 3 or seg.shape[0] != units.shape[0] or seg.shape[1] != units.shape[2]:
+            raise ValueError(f"stretch_planned: a plan of {units.shape[0]} rows of {units.shape[2]} frames expected, got seg {tuple(seg.shape)}")
+        return KU.useg_stretch(units, seg, plan["nsegs"], int(n_out), channel_dim=1)
 
     def __call__(self, units, clusters, boundaries, tgt_duartations):
         """units (1, D, T), sound types (N,), boundaries (N + 1,), target durations -> up/down sampled units (1, D, T')."""
