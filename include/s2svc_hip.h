@@ -1179,6 +1179,37 @@ int s2svc_hubert_conv0_apply(int dtype, int B, int Nmax, int pad, int L0max, con
 int s2svc_hubert_logits(int dtype, int B, int L, int K, int log_softmax, const void* units, const int32_t* lens, const float* emb, float* out,
                         void* stream);
 
+/* ========================================================================================== */
+/* Waveform conditioning (csrc/audio.hip): batched polyphase resampling and silence trimming   */
+/* of padded batches with per-row lengths.  fp32, inference only, no atomics; samples at or    */
+/* beyond lens[b] are never read; a batched row equals its own B = 1 call bit for bit.         */
+/* replaces: torchaudio.functional.resample (urhythmic/urhythmic_resample.py:27-31),           */
+/* librosa.effects.trim (urhythmic/urhythmic_convert.py:160-171, urhythmic_encode.py:122-133,  */
+/* bin/preprocess.py:207-221) and the global gain of bin/preprocess.py:250                     */
+/* ========================================================================================== */
+/* outputs per workgroup (1024) and the floats of LDS a workgroup may stage (12288), as the library states them */
+int s2svc_resample_tile(void);
+int s2svc_resample_max_span(void);
+/* out[b][q new + p] = sum_{k < Kb} taps[k][p] * x_b[q orig + first[p] + k - width], x_b = the first lens[b] samples of wav[b] and 0
+   outside them; fp32 FMA in ascending k.  wav (B, Nmax), out (B, Mmax): outputs at or beyond out_lens[b] are +0.  taps (Kb, new_) fp32
+   and first (new_) int32 with fmin <= first[p] <= fmax <= 2 width + orig (entries outside are clamped) are the banded table of
+   (orig, new_) after division by their gcd.  A workgroup stages ((new_ + tile - 2) / new_) orig + fmax - fmin + Kb samples: above
+   s2svc_resample_max_span() the call is refused.  One launch whatever B is. */
+int s2svc_resample_poly(int B, int Nmax, int Mmax, int orig, int new_, int width, int Kb, int fmin, int fmax, const float* wav,
+                        const int32_t* lens, const int32_t* out_lens, const float* taps, const int32_t* first, float* out, void* stream);
+/* power[b][i] (B, nfmax) double = mean of x^2 over the centred frame [i hop - frame_length / 2, .. + frame_length) of row b, i <= lens[b] / hop
+   (0 beyond); outside the row the frame reads zeros (reflect = 0) or the reflected row (reflect = 1: numpy's pad mode "reflect").
+   One wavefront per frame, an ordered double sum. */
+int s2svc_trim_frames(int B, int Nmax, int nfmax, int frame_length, int hop, int reflect, const float* wav, const int32_t* lens,
+                      double* power, void* stream);
+/* intervals (B, 2) int32 = (first hop, min(lens[b], (last + 1) hop)) over the frames i <= lens[b] / hop with
+   max(amin, power[b][i]) > max(amin, max_i power[b][i]) * ratio (double), (0, 0) when there is none.  One wave per row. */
+int s2svc_trim_intervals(int B, int Nmax, int nfmax, int hop, double amin, double ratio, const int32_t* lens, const double* power,
+                         int32_t* intervals, void* stream);
+/* out[b][i] (B, Mmax) = wav[b][start_b + i] * gain for i < end_b - start_b, +0 beyond; (start_b, end_b) = intervals[b] (device data),
+   clamped to [0, Nmax]. */
+int s2svc_wav_gather_rows(int B, int Nmax, int Mmax, float gain, const float* wav, const int32_t* intervals, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

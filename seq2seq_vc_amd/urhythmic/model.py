@@ -4,6 +4,7 @@ chained, convert_wavs."""
 import torch
 from torch import nn
 
+from .. import audio
 from ..ops import kernels_hubert as KH
 from ..ops import kernels_urhythmic as KU
 from .hubert import HubertSoft, _host_lens, _inference_only, _wav2
@@ -12,6 +13,7 @@ from .segmenter import Segmenter, _device_log_probs
 from .stretcher import TimeStretcherFineGrained
 from .utils import SILENCE
 
+SAMPLING_RATE = 16000        # what HuBERT-Soft takes (urhythmic_convert.py: SAMPLING_RATE)
 
 def _need_hubert(hubert):
     if not isinstance(hubert, HubertSoft):
@@ -142,9 +144,20 @@ class UrhythmicFine(nn.Module):
 
 
 @torch.inference_mode()
-def convert_wavs(hubert: HubertSoft, model: UrhythmicFine, wavs: torch.Tensor, lens, plan="device"):
+def convert_wavs(hubert: HubertSoft, model: UrhythmicFine, wavs: torch.Tensor, lens, plan="device", sample_rate=SAMPLING_RATE, trim=None):
     """Waveform to waveform: encode_batch, then model.convert_batch.  wavs (B, 1, Tmax), lens (B) samples of every row (list or CPU
     tensor) -> list of B converted waveforms (1-D).  Launches: HuBERT-Soft's + 4 of the search, plan and stretch + the vocoder's
-    (plan "device"), whatever B is; one device-to-host read (3 B ints)."""
+    (plan "device"), whatever B is; one device-to-host read (3 B ints).
+
+    sample_rate other than 16000 and / or trim = dict(top_db=, frame_length=, hop_length=[, pad_mode=]): the waveforms are conditioned
+    first as urhythmic_convert.py:160-171 does on the host (audio.condition_batch: resample to 16 kHz, then trim the silence): one
+    launch for the resampling, three and one more host read (2 B ints) for the trim.  With the defaults nothing is added."""
+    if sample_rate != SAMPLING_RATE or trim is not None:
+        config = dict(sampling_rate=SAMPLING_RATE, trim_silence=trim is not None)
+        if trim is not None:
+            trim = audio._trim_keys(trim)
+            config.update(trim_threshold_in_db=trim["top_db"], trim_frame_size=trim["frame_length"], trim_hop_size=trim["hop_length"],
+                          trim_pad_mode=trim.get("pad_mode", "constant"))
+        wavs, lens = audio.condition_batch(wavs, lens, sample_rate, config)
     units, log_probs, frame_lens = encode_batch(hubert, wavs, lens)
     return model.convert_batch(units, log_probs, frame_lens, plan=plan)
