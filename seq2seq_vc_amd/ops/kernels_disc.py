@@ -35,33 +35,33 @@ def chunks(rows):
     return -(-rows // CHUNK)
 
 
-def _f32(name, t, shape=None):
+def check_f32(name, t, shape=None):
     if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
         raise ValueError(f"{name}: contiguous fp32 {'' if shape is None else tuple(shape)} expected, got {t.dtype} {tuple(t.shape)}")
     return t
 
 
-def _flat(name, t, n):
+def check_flat(name, t, n):
     if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
         raise ValueError(f"{name}: contiguous fp32 with {n} values expected, got {t.dtype} {tuple(t.shape)}")
     return t
 
 
-def _out(name, out, shape, like):
+def out_or_empty(name, out, shape, like):
     if out is None:
         return torch.empty(shape, dtype=torch.float32, device=like.device)
     _need_cuda(out)
-    return _f32(name + " out", out, shape)
+    return check_f32(name + " out", out, shape)
 
 
 def disc_input(x, w32, bias, p, slope=0.1, out=None):
     """x (B, T) -> (B, L1, p, 32) = leaky_relu(conv(reflect-padded x viewed (L0, p), k 5, stride 3) + bias); w32 (32, 1, 5) folded."""
     _need_cuda(x, w32, bias)
-    B, T = _f32("disc_input x", x).shape
+    B, T = check_f32("disc_input x", x).shape
     L0, _ = folded_len(T, p)
-    _flat("disc_input w32", w32, C_FIRST * TAPS)
-    _f32("disc_input bias", bias, (C_FIRST,))
-    out = _out("disc_input", out, (B, out_len(L0, STRIDE), p, C_FIRST), x)
+    check_flat("disc_input w32", w32, C_FIRST * TAPS)
+    check_f32("disc_input bias", bias, (C_FIRST,))
+    out = out_or_empty("disc_input", out, (B, out_len(L0, STRIDE), p, C_FIRST), x)
     _lib.check(_lib.lib().s2svc_hifigan_disc_input(B, T, p, ptr(x), ptr(w32), ptr(bias), float(slope), ptr(out), stream()), "hifigan_disc_input")
     return out
 
@@ -71,10 +71,10 @@ def disc_conv(x, w_op, bias, cout, stride, slope=0.1, out=None):
     _need_cuda(x, w_op, bias)
     if x.dim() != 4:
         raise ValueError("disc_conv: x (B, L, p, C_in)")
-    B, L, p, cin = _f32("disc_conv x", x).shape
-    _flat("disc_conv w_op", w_op, cout * TAPS * cin_padded(cin))
-    _f32("disc_conv bias", bias, (cout,))
-    out = _out("disc_conv", out, (B, out_len(L, stride), p, cout), x)
+    B, L, p, cin = check_f32("disc_conv x", x).shape
+    check_flat("disc_conv w_op", w_op, cout * TAPS * cin_padded(cin))
+    check_f32("disc_conv bias", bias, (cout,))
+    out = out_or_empty("disc_conv", out, (B, out_len(L, stride), p, cout), x)
     _lib.check(_lib.lib().s2svc_hifigan_disc_conv(B, L, p, cin, cout, stride, ptr(x), ptr(w_op), ptr(bias), float(slope), ptr(out), stream()),
                "hifigan_disc_conv")
     return out
@@ -85,10 +85,10 @@ def disc_post(x, w, bias, out=None):
     _need_cuda(x, w, bias)
     if x.dim() != 4:
         raise ValueError("disc_post: x (B, L, p, C)")
-    B, L, p, C = _f32("disc_post x", x).shape
-    _flat("disc_post w", w, POST_TAPS * C)
-    _f32("disc_post bias", bias, (1,))
-    y = _out("disc_post", out, (B, L * p), x)
+    B, L, p, C = check_f32("disc_post x", x).shape
+    check_flat("disc_post w", w, POST_TAPS * C)
+    check_f32("disc_post bias", bias, (1,))
+    y = out_or_empty("disc_post", out, (B, L * p), x)
     _lib.check(_lib.lib().s2svc_hifigan_disc_post(B, L, p, C, ptr(x), ptr(w), ptr(bias), ptr(y), stream()), "hifigan_disc_post")
     return y
 
@@ -97,16 +97,16 @@ def disc_post_bwd(x, w, dy1=None, dy2=None, add=None, slope=0.1, out=None):
     """Backward of disc_post: d = dy1 + dy2 ((B, L * p) each or None) -> (dx (B, L, p, C) = leaky_relu'(x) * (add + data gradient),
     wpart (chunks, 3, C), bpart (chunks,)); add = the gradient of the feature x itself, or None."""
     _need_cuda(x, w, dy1, dy2, add)
-    B, L, p, C = _f32("disc_post_bwd x", x).shape
-    _flat("disc_post_bwd w", w, POST_TAPS * C)
+    B, L, p, C = check_f32("disc_post_bwd x", x).shape
+    check_flat("disc_post_bwd w", w, POST_TAPS * C)
     for name, t in (("dy1", dy1), ("dy2", dy2)):
         if t is not None:
-            _flat("disc_post_bwd " + name, t, B * L * p)
+            check_flat("disc_post_bwd " + name, t, B * L * p)
     if add is not None:
-        _f32("disc_post_bwd add", add, x.shape)
+        check_f32("disc_post_bwd add", add, x.shape)
     nch = chunks(B * L * p)
     shapes = (tuple(x.shape), (nch, POST_TAPS, C), (nch,))
-    outs = [_out("disc_post_bwd", None if out is None else out[i], shapes[i], x) for i in range(3)]
+    outs = [out_or_empty("disc_post_bwd", None if out is None else out[i], shapes[i], x) for i in range(3)]
     _lib.check(_lib.lib().s2svc_hifigan_disc_post_bwd(B, L, p, C, ptr(x), ptr(w), ptr(dy1), ptr(dy2), ptr(add), float(slope), ptr(outs[0]),
                                                       ptr(outs[1]), ptr(outs[2]), stream()), "hifigan_disc_post_bwd")
     return tuple(outs)
@@ -116,13 +116,13 @@ def disc_wgrad(dy, x, stride, out=None):
     """Partials of the weight / bias gradients of disc_conv: dy (B, Lo, p, C_out) gradient of the pre-activation, x (B, L, p, C_in) ->
     (wpart (chunks, C_out, 5, C_in), bpart (chunks, C_out)), chunks of 256 rows of B * Lo * p in ascending order."""
     _need_cuda(dy, x)
-    B, L, p, cin = _f32("disc_wgrad x", x).shape
+    B, L, p, cin = check_f32("disc_wgrad x", x).shape
     cout = dy.shape[-1]
     Lo = out_len(L, stride)
-    _f32("disc_wgrad dy", dy, (B, Lo, p, cout))
+    check_f32("disc_wgrad dy", dy, (B, Lo, p, cout))
     nch = chunks(B * Lo * p)
     shapes = ((nch, cout, TAPS, cin), (nch, cout))
-    outs = [_out("disc_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
+    outs = [out_or_empty("disc_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
     _lib.check(_lib.lib().s2svc_hifigan_disc_wgrad(B, L, p, cin, cout, stride, ptr(dy), ptr(x), ptr(outs[0]), ptr(outs[1]), stream()),
                "hifigan_disc_wgrad")
     return tuple(outs)
@@ -134,14 +134,14 @@ def disc_dgrad(dy, w_opT, L, cin, stride, mask_src=None, add=None, slope=0.1, ou
     _need_cuda(dy, w_opT, mask_src, add)
     if dy.dim() != 4:
         raise ValueError("disc_dgrad: dy (B, Lo, p, C_out)")
-    B, Lo, p, cout = _f32("disc_dgrad dy", dy).shape
+    B, Lo, p, cout = check_f32("disc_dgrad dy", dy).shape
     if Lo != out_len(L, stride):
         raise ValueError(f"disc_dgrad: dy has {Lo} rows along L, the convolution of {L} rows gives {out_len(L, stride)}")
-    _flat("disc_dgrad w_opT", w_opT, cin * TAPS * cin_padded(cout))
+    check_flat("disc_dgrad w_opT", w_opT, cin * TAPS * cin_padded(cout))
     for name, t in (("mask_src", mask_src), ("add", add)):
         if t is not None:
-            _f32("disc_dgrad " + name, t, (B, L, p, cin))
-    dx = _out("disc_dgrad", out, (B, L, p, cin), dy)
+            check_f32("disc_dgrad " + name, t, (B, L, p, cin))
+    dx = out_or_empty("disc_dgrad", out, (B, L, p, cin), dy)
     _lib.check(_lib.lib().s2svc_hifigan_disc_dgrad(B, L, p, cin, cout, stride, ptr(dy), ptr(w_opT), ptr(mask_src), ptr(add), float(slope),
                                                    ptr(dx), stream()), "hifigan_disc_dgrad")
     return dx
@@ -150,12 +150,12 @@ def disc_dgrad(dy, w_opT, L, cin, stride, mask_src=None, add=None, slope=0.1, ou
 def disc_input_wgrad(dy, x, p, out=None):
     """Partials of the input layer: dy (B, L1, p, 32), x (B, T) -> (wpart (chunks, 32, 5, 1), bpart (chunks, 32))."""
     _need_cuda(dy, x)
-    B, T = _f32("disc_input_wgrad x", x).shape
+    B, T = check_f32("disc_input_wgrad x", x).shape
     L1 = out_len(folded_len(T, p)[0], STRIDE)
-    _f32("disc_input_wgrad dy", dy, (B, L1, p, C_FIRST))
+    check_f32("disc_input_wgrad dy", dy, (B, L1, p, C_FIRST))
     nch = chunks(B * L1 * p)
     shapes = ((nch, C_FIRST, TAPS, 1), (nch, C_FIRST))
-    outs = [_out("disc_input_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
+    outs = [out_or_empty("disc_input_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
     _lib.check(_lib.lib().s2svc_hifigan_disc_input_wgrad(B, T, p, ptr(dy), ptr(x), ptr(outs[0]), ptr(outs[1]), stream()),
                "hifigan_disc_input_wgrad")
     return tuple(outs)
@@ -168,8 +168,8 @@ def disc_input_dgrad(dy, w32, T, p, out=None):
     if dy.dim() != 4:
         raise ValueError("disc_input_dgrad: dy (B, L1, p, 32)")
     B = dy.shape[0]
-    _f32("disc_input_dgrad dy", dy, (B, L1, p, C_FIRST))
-    _flat("disc_input_dgrad w32", w32, C_FIRST * TAPS)
-    dx = _out("disc_input_dgrad", out, (B, T), dy)
+    check_f32("disc_input_dgrad dy", dy, (B, L1, p, C_FIRST))
+    check_flat("disc_input_dgrad w32", w32, C_FIRST * TAPS)
+    dx = out_or_empty("disc_input_dgrad", out, (B, T), dy)
     _lib.check(_lib.lib().s2svc_hifigan_disc_input_dgrad(B, T, p, ptr(dy), ptr(w32), ptr(dx), stream()), "hifigan_disc_input_dgrad")
     return dx

@@ -7,7 +7,7 @@ import torch
 
 from .. import _lib
 from .kernels import _need_cuda, ptr, stream
-from .kernels_disc import _f32, _flat, _out
+from .kernels_disc import check_f32, check_flat, out_or_empty
 from .kernels_vocoder import cin_padded
 
 TAPS, PAD = 41, 20                         # kernel size and padding of the grouped convolutions convs[1..5]
@@ -40,8 +40,8 @@ def msd_pool(x, out=None):
     _need_cuda(x)
     if x.dim() != 2:
         raise ValueError("msd_pool: x (B, T)")
-    B, T = _f32("msd_pool x", x).shape
-    y = _out("msd_pool", out, (B, pool_len(T)), x)
+    B, T = check_f32("msd_pool x", x).shape
+    y = out_or_empty("msd_pool", out, (B, pool_len(T)), x)
     _lib.check(_lib.lib().s2svc_hifigan_msd_pool(B, T, ptr(x), ptr(y), stream()), "hifigan_msd_pool")
     return y
 
@@ -52,8 +52,8 @@ def msd_pool_bwd(dy, T, out=None):
     if dy.dim() != 2:
         raise ValueError("msd_pool_bwd: dy (B, T // 2 + 1)")
     B = dy.shape[0]
-    _f32("msd_pool_bwd dy", dy, (B, pool_len(T)))
-    dx = _out("msd_pool_bwd", out, (B, T), dy)
+    check_f32("msd_pool_bwd dy", dy, (B, pool_len(T)))
+    dx = out_or_empty("msd_pool_bwd", out, (B, T), dy)
     _lib.check(_lib.lib().s2svc_hifigan_msd_pool_bwd(B, T, ptr(dy), ptr(dx), stream()), "hifigan_msd_pool_bwd")
     return dx
 
@@ -63,10 +63,10 @@ def msd_input(x, w32, bias, slope=0.1, out=None):
     _need_cuda(x, w32, bias)
     if x.dim() != 2:
         raise ValueError("msd_input: x (B, T)")
-    B, T = _f32("msd_input x", x).shape
-    _flat("msd_input w32", w32, C_FIRST * IN_TAPS)
-    _f32("msd_input bias", bias, (C_FIRST,))
-    out = _out("msd_input", out, (B, T, C_FIRST), x)
+    B, T = check_f32("msd_input x", x).shape
+    check_flat("msd_input w32", w32, C_FIRST * IN_TAPS)
+    check_f32("msd_input bias", bias, (C_FIRST,))
+    out = out_or_empty("msd_input", out, (B, T, C_FIRST), x)
     _lib.check(_lib.lib().s2svc_hifigan_msd_input(B, T, ptr(x), ptr(w32), ptr(bias), float(slope), ptr(out), stream()), "hifigan_msd_input")
     return out
 
@@ -74,11 +74,11 @@ def msd_input(x, w32, bias, slope=0.1, out=None):
 def msd_input_wgrad(dy, x, out=None):
     """Partials of the input layer: dy (B, T, 128), x (B, T) -> (wpart (chunks, 128, 15, 1), bpart (chunks, 128)), chunks of 256 rows."""
     _need_cuda(dy, x)
-    B, T = _f32("msd_input_wgrad x", x).shape
-    _f32("msd_input_wgrad dy", dy, (B, T, C_FIRST))
+    B, T = check_f32("msd_input_wgrad x", x).shape
+    check_f32("msd_input_wgrad dy", dy, (B, T, C_FIRST))
     nch = -(-B * T // IN_CHUNK)
     shapes = ((nch, C_FIRST, IN_TAPS, 1), (nch, C_FIRST))
-    outs = [_out("msd_input_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
+    outs = [out_or_empty("msd_input_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
     _lib.check(_lib.lib().s2svc_hifigan_msd_input_wgrad(B, T, ptr(dy), ptr(x), ptr(outs[0]), ptr(outs[1]), stream()), "hifigan_msd_input_wgrad")
     return tuple(outs)
 
@@ -89,9 +89,9 @@ def msd_input_dgrad(dy, w32, out=None):
     if dy.dim() != 3:
         raise ValueError("msd_input_dgrad: dy (B, T, 128)")
     B, T = dy.shape[:2]
-    _f32("msd_input_dgrad dy", dy, (B, T, C_FIRST))
-    _flat("msd_input_dgrad w32", w32, C_FIRST * IN_TAPS)
-    dx = _out("msd_input_dgrad", out, (B, T), dy)
+    check_f32("msd_input_dgrad dy", dy, (B, T, C_FIRST))
+    check_flat("msd_input_dgrad w32", w32, C_FIRST * IN_TAPS)
+    dx = out_or_empty("msd_input_dgrad", out, (B, T), dy)
     _lib.check(_lib.lib().s2svc_hifigan_msd_input_dgrad(B, T, ptr(dy), ptr(w32), ptr(dx), stream()), "hifigan_msd_input_dgrad")
     return dx
 
@@ -110,11 +110,11 @@ def msd_gconv(x, w_op, bias, cout, groups, stride, slope=0.1, out=None):
     _need_cuda(x, w_op, bias)
     if x.dim() != 3:
         raise ValueError("msd_gconv: x (B, L, C_in)")
-    B, L, cin = _f32("msd_gconv x", x).shape
+    B, L, cin = check_f32("msd_gconv x", x).shape
     cg, _ = _gshape("msd_gconv", cin, cout, groups, stride)
-    _flat("msd_gconv w_op", w_op, cout * TAPS * cin_padded(cg))
-    _f32("msd_gconv bias", bias, (cout,))
-    out = _out("msd_gconv", out, (B, out_len(L, stride), cout), x)
+    check_flat("msd_gconv w_op", w_op, cout * TAPS * cin_padded(cg))
+    check_f32("msd_gconv bias", bias, (cout,))
+    out = out_or_empty("msd_gconv", out, (B, out_len(L, stride), cout), x)
     _lib.check(_lib.lib().s2svc_hifigan_msd_gconv(B, L, cin, cout, groups, stride, ptr(x), ptr(w_op), ptr(bias), float(slope), ptr(out), stream()),
                "hifigan_msd_gconv")
     return out
@@ -125,10 +125,10 @@ def msd_fold_bwd(w32, groups, out=None):
     _need_cuda(w32)
     if w32.dim() != 3 or w32.shape[2] != TAPS:
         raise ValueError("msd_fold_bwd: w32 (C_out, C_in / groups, 41)")
-    cout, cg, _ = _f32("msd_fold_bwd w32", w32).shape
+    cout, cg, _ = check_f32("msd_fold_bwd w32", w32).shape
     if groups < 1 or cout % groups:
         raise ValueError("msd_fold_bwd: C_out divisible by the groups")
-    op = _out("msd_fold_bwd", out, (cg * groups, TAPS * cin_padded(cout // groups)), w32)
+    op = out_or_empty("msd_fold_bwd", out, (cg * groups, TAPS * cin_padded(cout // groups)), w32)
     _lib.check(_lib.lib().s2svc_hifigan_msd_fold_bwd(cg * groups, cout, groups, ptr(w32), ptr(op), stream()), "hifigan_msd_fold_bwd")
     return op
 
@@ -138,15 +138,15 @@ def msd_gconv_dgrad(dy, w_opT, L, cin, groups, stride, mask_src=None, add=None, 
     _need_cuda(dy, w_opT, mask_src, add)
     if dy.dim() != 3:
         raise ValueError("msd_gconv_dgrad: dy (B, Lo, C_out)")
-    B, Lo, cout = _f32("msd_gconv_dgrad dy", dy).shape
+    B, Lo, cout = check_f32("msd_gconv_dgrad dy", dy).shape
     if Lo != out_len(L, stride):
         raise ValueError(f"msd_gconv_dgrad: dy has {Lo} rows, the convolution of {L} rows gives {out_len(L, stride)}")
     _, og = _gshape("msd_gconv_dgrad", cin, cout, groups, stride)
-    _flat("msd_gconv_dgrad w_opT", w_opT, cin * TAPS * cin_padded(og))
+    check_flat("msd_gconv_dgrad w_opT", w_opT, cin * TAPS * cin_padded(og))
     for name, t in (("mask_src", mask_src), ("add", add)):
         if t is not None:
-            _f32("msd_gconv_dgrad " + name, t, (B, L, cin))
-    dx = _out("msd_gconv_dgrad", out, (B, L, cin), dy)
+            check_f32("msd_gconv_dgrad " + name, t, (B, L, cin))
+    dx = out_or_empty("msd_gconv_dgrad", out, (B, L, cin), dy)
     _lib.check(_lib.lib().s2svc_hifigan_msd_gconv_dgrad(B, L, cin, cout, groups, stride, ptr(dy), ptr(w_opT), ptr(mask_src), ptr(add), float(slope),
                                                         ptr(dx), stream()), "hifigan_msd_gconv_dgrad")
     return dx
@@ -158,14 +158,14 @@ def msd_gconv_wgrad(dy, x, groups, stride, out=None):
     _need_cuda(dy, x)
     if x.dim() != 3 or dy.dim() != 3:
         raise ValueError("msd_gconv_wgrad: dy (B, Lo, C_out), x (B, L, C_in)")
-    B, L, cin = _f32("msd_gconv_wgrad x", x).shape
+    B, L, cin = check_f32("msd_gconv_wgrad x", x).shape
     cout = dy.shape[-1]
     cg, _ = _gshape("msd_gconv_wgrad", cin, cout, groups, stride)
     Lo = out_len(L, stride)
-    _f32("msd_gconv_wgrad dy", dy, (B, Lo, cout))
+    check_f32("msd_gconv_wgrad dy", dy, (B, Lo, cout))
     nch = gconv_chunks(B, Lo)
     shapes = ((nch, cout, TAPS, cg), (nch, cout))
-    outs = [_out("msd_gconv_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
+    outs = [out_or_empty("msd_gconv_wgrad", None if out is None else out[i], shapes[i], x) for i in range(2)]
     _lib.check(_lib.lib().s2svc_hifigan_msd_gconv_wgrad(B, L, cin, cout, groups, stride, gconv_chunk(Lo), ptr(dy), ptr(x), ptr(outs[0]), ptr(outs[1]),
                                                         stream()), "hifigan_msd_gconv_wgrad")
     return tuple(outs)
@@ -177,9 +177,9 @@ def _sn_args(name, W, u, v):
         raise ValueError(f"{name}: W (O, ...)")
     O = W.shape[0]
     K = W.numel() // O
-    _f32(name + " W", W)
-    _f32(name + " u", u, (O,))
-    _f32(name + " v", v, (K,))
+    check_f32(name + " W", W)
+    check_f32(name + " u", u, (O,))
+    check_f32(name + " v", v, (K,))
     return O, K
 
 
@@ -187,7 +187,7 @@ def msd_sn_power(W, u, v, iterate, eps=SN_EPS, out=None):
     """One power iteration of spectral norm on W (O, ...) viewed (O, K): with `iterate`, v and u are updated IN PLACE; -> sigma (1,) on the
     device (= u . W v), no host read.  iterate False leaves u and v untouched."""
     O, K = _sn_args("msd_sn_power", W, u, v)
-    sigma = _out("msd_sn_power", out, (1,), W)
+    sigma = out_or_empty("msd_sn_power", out, (1,), W)
     ws = torch.empty(O + K, dtype=torch.float64, device=W.device)
     _lib.check(_lib.lib().s2svc_hifigan_msd_sn_power(O, K, int(bool(iterate)), float(eps), ptr(W), ptr(u), ptr(v), ptr(sigma), ptr(ws), stream()),
                "hifigan_msd_sn_power")
@@ -197,9 +197,9 @@ def msd_sn_power(W, u, v, iterate, eps=SN_EPS, out=None):
 def msd_sn_scale(W, sigma, out=None):
     """W / sigma in W's shape."""
     _need_cuda(W, sigma)
-    _f32("msd_sn_scale W", W)
-    _f32("msd_sn_scale sigma", sigma, (1,))
-    w = _out("msd_sn_scale", out, tuple(W.shape), W)
+    check_f32("msd_sn_scale W", W)
+    check_f32("msd_sn_scale sigma", sigma, (1,))
+    w = out_or_empty("msd_sn_scale", out, tuple(W.shape), W)
     _lib.check(_lib.lib().s2svc_hifigan_msd_sn_scale(W.numel(), ptr(W), ptr(sigma), ptr(w), stream()), "hifigan_msd_sn_scale")
     return w
 
@@ -208,9 +208,9 @@ def msd_sn_finish(dW, W, u, v, sigma, out=None):
     """grad of weight_orig from dW = the gradient of W / sigma (u, v constants): dW / sigma - (sum(dW * W) / sigma^2) u v^T, in W's shape."""
     O, K = _sn_args("msd_sn_finish", W, u, v)
     _need_cuda(dW, sigma)
-    _f32("msd_sn_finish dW", dW, tuple(W.shape))
-    _f32("msd_sn_finish sigma", sigma, (1,))
-    grad = _out("msd_sn_finish", out, tuple(W.shape), W)
+    check_f32("msd_sn_finish dW", dW, tuple(W.shape))
+    check_f32("msd_sn_finish sigma", sigma, (1,))
+    grad = out_or_empty("msd_sn_finish", out, tuple(W.shape), W)
     ws = torch.empty(O, dtype=torch.float64, device=W.device)
     _lib.check(_lib.lib().s2svc_hifigan_msd_sn_finish(O, K, ptr(dW), ptr(W), ptr(u), ptr(v), ptr(sigma), ptr(grad), ptr(ws), stream()),
                "hifigan_msd_sn_finish")

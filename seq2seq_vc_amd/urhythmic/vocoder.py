@@ -10,19 +10,24 @@ discriminator, or its `mpd.*` / `msd.*` subtree, loads as it is.  The three loss
 of this file, one autograd node and one table-driven launch sequence each (csrc/gan_loss.hip); the optimiser is optim.MultiAdamW and
 the whole loop body is urhythmic/fine_tune.py.
 
-A ScaleDiscriminator call is ONE autograd node as well (inputs x and its 16 or 24 parameters, outputs the score and eight features);
-the average pool between the scales is a small node of its own.  The spectrally normed scale runs one power iteration per call in
-train() mode (under no_grad too) and writes u, v back into its buffers, as torch.nn.utils.spectral_norm does; the state kept for
-the backward holds copies of the u, v and sigma that the call used.
+PeriodDiscriminator and ScaleDiscriminator are one executor, `_Discriminator`: `launch_plan()` / `backward_plan()` list the launches
+of one call as dicts, and the forward and the backward walk that list through one table from `kind` to handler.  The launches both
+halves share (the weight-norm fold, the 5-tap convolution, conv_post, their backward) have one handler each, written for the period
+half's 4-D buffers; a class says how its stored buffers become that view (`_four` / `_stored`: the identity there, `unsqueeze(2)` /
+`squeeze(2)` in the scale half, whose layer 6 and conv_post are the period kernels at p = 1) and registers the kinds it has alone.
+The lists are built once per module and mode (`_plan`): a call walks the stored list.
 
-Activations are channel-last (B, L, p, C); the features handed out are strided (B, C, L, p) views of them and the score is the
-flattening of the last one.  Under grad mode a PeriodDiscriminator call is ONE autograd node whose inputs are x and the 18
-parameters and whose outputs are the score and the six features; its backward takes whichever of the seven gradients arrive, in
-any strides (channel-last-strided ones are read in place, others go through one copy), and returns the parameter gradients and --
-when x requires grad -- dx, which flows on into `HifiganGenerator.trainable()`.  There is no CPU path and no bf16 path: a bf16
-forward flips leaky-relu masks, which alone puts the gradients several per cent off.
-`launch_plan()` / `backward_plan()` list the launches of one call."""
+Activations are channel-last, (B, L, p, C) or (B, L, C); the features handed out are strided (B, C, L, p) / (B, C, L) views of them
+and the score is the flattening of the last one.  Under grad mode a call is ONE autograd node whose inputs are x and the parameters
+(18 per period; 16, or 24 under spectral norm, per scale) and whose outputs are the score and the six or eight features; its backward
+takes whichever of the gradients arrive, in any strides (channel-last-strided ones are read in place, others go through one copy),
+and returns the parameter gradients and -- when x requires grad -- dx, which flows on into `HifiganGenerator.trainable()`.  The
+average pool between the scales is a small node of its own.  The spectrally normed scale runs one power iteration per call in
+train() mode (under no_grad too) and writes u, v back into its buffers, as torch.nn.utils.spectral_norm does; the state kept for
+the backward holds copies of the u, v and sigma that the call used.  There is no CPU path and no bf16 path: a bf16 forward flips
+leaky-relu masks, which alone puts the gradients several per cent off."""
 import math
+from types import SimpleNamespace
 
 import torch
 from torch import nn
@@ -40,21 +45,21 @@ KINDS = ("fold", "input", "conv", "post")
 BWD_KINDS = ("post_bwd", "wgrad", "input_wgrad", "finish", "fold_bwd", "dgrad", "input_dgrad")
 
 
-class _WNConv2d(nn.Module):
-    """Parameters of weight_norm(Conv2d(cin, cout, (k, 1))) in the reference's checkpoint form, torch's default initialisation."""
+class _WNConv(nn.Module):
+    """Parameters of a weight-normed convolution in the reference's checkpoint form, torch's default initialisation: `shape` is
+    (O, C, k, 1) for weight_norm(Conv2d(C, O, (k, 1))) and (O, C / groups, k) for weight_norm(Conv1d(C, O, k, groups=groups))."""
 
-    def __init__(self, cin, cout, k):
+    def __init__(self, shape):
         super().__init__()
-        bound = 1.0 / math.sqrt(cin * k)
-        v = torch.empty(cout, cin, k, 1).uniform_(-bound, bound)
-        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1, 1))
+        bound = 1.0 / math.sqrt(shape[1] * shape[2])
+        v = torch.empty(*shape).uniform_(-bound, bound)
+        self.bias = nn.Parameter(torch.empty(shape[0]).uniform_(-bound, bound))
+        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, *[1] * (len(shape) - 1)))
         self.weight_v = nn.Parameter(v)
 
     def vg(self):
         """(v (O, C, k), g (O)) fp32 contiguous views of the live parameters"""
-        v = self.weight_v.detach()
-        return v.contiguous().view(v.shape[0], v.shape[1], v.shape[2]), self.weight_g.detach().contiguous().view(-1)
+        return self.weight_v.detach().contiguous().flatten(2), self.weight_g.detach().contiguous().view(-1)
 
 
 def layer_lengths(T, p):
@@ -65,8 +70,17 @@ def layer_lengths(T, p):
     return L
 
 
-class _PeriodFunction(torch.autograd.Function):
-    """One PeriodDiscriminator call as ONE autograd node: inputs x and the 18 parameters, outputs the score and the six features."""
+class _Layer:
+    """What one call holds of a layer: v, g = the parameters' views (v = weight_orig and g = None under spectral norm), bias, w32 =
+    the folded weight, op = the GEMM operand, and under spectral norm sigma and uv = copies of the u, v the call used."""
+    __slots__ = ("v", "g", "bias", "w32", "op", "sigma", "uv")
+
+    def __init__(self, v, g, bias, w32=None, op=None, sigma=None, uv=None):
+        self.v, self.g, self.bias, self.w32, self.op, self.sigma, self.uv = v, g, bias, w32, op, sigma, uv
+
+
+class _DiscFunction(torch.autograd.Function):
+    """One discriminator call as ONE autograd node: inputs x and the parameters, outputs the score and the features."""
 
     @staticmethod
     def forward(ctx, disc, x, *params):
@@ -85,9 +99,147 @@ class _PeriodFunction(torch.autograd.Function):
         return (None, dx) + tuple(grads)
 
 
-class PeriodDiscriminator(nn.Module):
+class _PeriodFunction(_DiscFunction):
+    """One PeriodDiscriminator call: inputs x and the 18 parameters, outputs the score and the six features."""
+
+
+class _ScaleFunction(_DiscFunction):
+    """One ScaleDiscriminator call: inputs x and the 16 or 24 parameters, outputs the score and the eight features."""
+
+
+def _flat(g, B):
+    return None if g is None else g.detach().float().reshape(B, -1).contiguous()
+
+
+class _Discriminator(nn.Module):
+    """The executor of both discriminator halves.  A subclass has `convs`, `conv_post`, `launch_plan()` and `backward_plan()`, names
+    its autograd node (`_FUNCTION`), the permutations between its stored buffers and the caller's features (`_TO_CALLER`,
+    `_FROM_CALLER`), `_four` / `_stored`, and extends `_HANDLERS` by the kinds of its own.  A handler is `f(self, c, e)`: c = the
+    state of the call (ops: layer -> _Layer, bufs: index -> stored activation, x (B, T), keep; in the backward also gf = the features'
+    gradients channel-last, gscore, glast, out: layer -> (gw, gg, gb), and parts, dpre, opT, dx = what one launch hands the next)."""
+    _MIN_T = 0
+
+    def _plan(self, *flags):
+        """launch_plan() or, with (need_dx, need_params), backward_plan(): built once per train() / eval() mode and flags"""
+        key = (self.training,) + flags
+        plans = self.__dict__.setdefault("_plans", {})
+        if key not in plans:
+            plans[key] = self.backward_plan(*flags) if flags else self.launch_plan()
+        return plans[key]
+
+    def _leaf(self, name):
+        return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
+
+    def _check(self, x):
+        name = type(self).__name__
+        if x.dim() != 3 or x.shape[1] != 1 or x.shape[2] < self._MIN_T:
+            raise ValueError(f"{name}: x (B, 1, T) expected, got {tuple(x.shape)}")
+        dtypes = {x.dtype} | {p.dtype for p in self.parameters()} | {b.dtype for b in self.buffers()}
+        if torch.bfloat16 in dtypes or torch.float16 in dtypes:
+            raise NotImplementedError(f"{name} runs in fp32 only: a 16-bit forward flips leaky-relu masks, which alone puts the "
+                                      "gradients several per cent off (DESIGN.md section 8)")
+        if dtypes != {torch.float32}:
+            raise TypeError(f"{name}: float32 input and parameters")
+        if not x.is_cuda or not self.conv_post.bias.is_cuda:
+            raise RuntimeError(f"{name} needs GPU tensors and GPU parameters (there is no CPU path)")
+
+    def _run(self, x, keep=False):
+        """-> (score, feats, state): executes launch_plan().  keep: the state also holds what the backward reads (the folded weights,
+        the parameters' views, the input, and copies of the u, v, sigma this call used)."""
+        B, _, T = x.shape
+        with torch.no_grad():
+            c = SimpleNamespace(ops={}, bufs={}, x=x.detach().reshape(B, T).contiguous(), keep=keep)
+            for e in self._plan():
+                self._HANDLERS[e["kind"]](self, c, e)
+            n = len(self.convs)
+            feats = [c.bufs[j].permute(*self._TO_CALLER) for j in range(n + 1)]
+            score = c.bufs[n].view(B, -1)
+        return score, feats, (c if keep else None)
+
+    def _backward(self, state, gscore, gfeats, need_dx, need_params):
+        """(dx or None, the parameter gradients in named_parameters() order or Nones) from whichever of the output gradients
+        arrived: executes backward_plan()."""
+        n = len(self.convs)
+
+        def channel_last(g):
+            """a feature's gradient as a contiguous stored buffer: in place when it already is channel-last-strided, else one copy"""
+            if g is None:
+                return None
+            g = g.detach().float().permute(*self._FROM_CALLER)
+            return g if g.is_contiguous() else g.contiguous()
+
+        c = SimpleNamespace(ops=state.ops, bufs=state.bufs, x=state.x, gf=[channel_last(g) for g in gfeats[:n]], gscore=gscore,
+                            glast=gfeats[n], out={}, parts=None, dpre=None, opT=None, dx=None)
+        with torch.no_grad():
+            for e in self._plan(bool(need_dx), bool(need_params)):
+                self._HANDLERS[e["kind"]](self, c, e)
+        grads = []
+        for name, prm in self.named_parameters():
+            if not need_params:
+                grads.append(None)
+                continue
+            layer, leaf = name.rsplit(".", 1)
+            gw, gg, gb = c.out[layer]
+            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
+        return c.dx, grads
+
+    def forward(self, x):
+        self._check(x)
+        params = [prm for _, prm in self.named_parameters()]
+        if torch.is_grad_enabled() and (x.requires_grad or any(prm.requires_grad for prm in params)):
+            res = self._FUNCTION.apply(self, x, *params)
+            return res[0], list(res[1:])
+        score, feats, _ = self._run(x)
+        return score, feats
+
+    # ---- the launches both halves have: the period half's launchers on the 4-D view of the buffers ---------------------------
+    def _do_fold(self, c, e):
+        layer, leaf = e["layer"], self._leaf(e["layer"])
+        first = layer == "convs.0"                # the input layer reads the folded weight itself, the others the GEMM operand
+        v, g = leaf.vg()
+        w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=first or (c.keep and e["mode"] == 0), want_op=not first)
+        c.ops[layer] = _Layer(v, g, leaf.bias.detach().contiguous(), w32, op)
+
+    def _do_conv(self, c, e):
+        o = c.ops[e["layer"]]
+        c.bufs[e["dst"]] = self._stored(KD.disc_conv(self._four(c.bufs[e["src"]]), o.op, o.bias, e["cout"], e["stride"], slope=LRELU_SLOPE))
+
+    def _do_post(self, c, e):
+        o, src = c.ops[e["layer"]], c.bufs[e["src"]]
+        c.bufs[e["dst"]] = KD.disc_post(self._four(src), o.op, o.bias).view(src.shape[:-1] + (1,))
+
+    def _do_post_bwd(self, c, e):
+        B = c.x.shape[0]
+        dpre, wp, bp = KD.disc_post_bwd(self._four(c.bufs[e["src"]]), c.ops[e["layer"]].op, dy1=_flat(c.gscore, B), dy2=_flat(c.glast, B),
+                                        add=self._four(c.gf[e["src"]]), slope=LRELU_SLOPE)
+        c.dpre, c.parts = self._stored(dpre), (wp, bp)
+
+    def _do_wgrad(self, c, e):
+        c.parts = KD.disc_wgrad(self._four(c.dpre), self._four(c.bufs[e["src"]]), e["stride"])
+
+    def _do_finish(self, c, e):
+        o = c.ops[e["layer"]]
+        c.out[e["layer"]] = KV.hifigan_wgrad_finish(e["mode"], c.parts[0], c.parts[1], o.v, o.g)
+        c.parts = None
+
+    def _do_fold_bwd(self, c, e):
+        c.opT = KV.hifigan_fold_bwd(0, c.ops[e["layer"]].w32, torch.float32)
+
+    def _do_dgrad(self, c, e):
+        mask = c.bufs[e["mask"]]
+        c.dpre = self._stored(KD.disc_dgrad(self._four(c.dpre), c.opT, mask.shape[1], e["cin"], e["stride"], mask_src=self._four(mask),
+                                            add=self._four(c.gf[e["mask"]]), slope=LRELU_SLOPE))
+        c.opT = None
+
+    _HANDLERS = dict(fold=_do_fold, conv=_do_conv, post=_do_post, post_bwd=_do_post_bwd, wgrad=_do_wgrad, finish=_do_finish,
+                     fold_bwd=_do_fold_bwd, dgrad=_do_dgrad)
+
+
+class PeriodDiscriminator(_Discriminator):
     """HiFi-GAN period discriminator (reference urhythmic/vocoder.py:211-293).  x (B, 1, T) fp32 on the device ->
     (score (B, L5 * p), [six features (B, C, L, p)])."""
+    _FUNCTION = _PeriodFunction
+    _TO_CALLER, _FROM_CALLER = (0, 3, 1, 2), (0, 2, 3, 1)
 
     def __init__(self, period, kernel_size=5, stride=3, use_spectral_norm=False):
         super().__init__()
@@ -98,8 +250,8 @@ class PeriodDiscriminator(nn.Module):
         if int(period) < 1:
             raise ValueError("PeriodDiscriminator: period >= 1")
         self.period = int(period)
-        self.convs = nn.ModuleList([_WNConv2d(CHANNELS[j], CHANNELS[j + 1], kernel_size) for j in range(len(STRIDES))])
-        self.conv_post = _WNConv2d(CHANNELS[-1], 1, KD.POST_TAPS)
+        self.convs = nn.ModuleList([_WNConv((CHANNELS[j + 1], CHANNELS[j], kernel_size, 1)) for j in range(len(STRIDES))])
+        self.conv_post = _WNConv((1, CHANNELS[-1], KD.POST_TAPS, 1))
 
     # ---- the launch lists -------------------------------------------------------------------------------------------------
     def launch_plan(self):
@@ -133,112 +285,28 @@ class PeriodDiscriminator(nn.Module):
             plan.append(dict(kind="input_dgrad", layer="convs.0"))
         return plan
 
-    # ---- execution --------------------------------------------------------------------------------------------------------
-    def _leaf(self, name):
-        return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
-
+    # ---- execution: the buffers are (B, L, p, C) as the launchers take them ---------------------------------------------------
     def _check(self, x):
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError(f"PeriodDiscriminator: x (B, 1, T) expected, got {tuple(x.shape)}")
-        dtypes = {x.dtype} | {p.dtype for p in self.parameters()}
-        if torch.bfloat16 in dtypes or torch.float16 in dtypes:
-            raise NotImplementedError("PeriodDiscriminator runs in fp32 only: a 16-bit forward flips leaky-relu masks, which alone puts the "
-                                      "gradients several per cent off (DESIGN.md section 8)")
-        if dtypes != {torch.float32}:
-            raise TypeError("PeriodDiscriminator: float32 input and parameters")
-        if not x.is_cuda or not self.conv_post.bias.is_cuda:
-            raise RuntimeError("PeriodDiscriminator needs GPU tensors and GPU parameters (there is no CPU path)")
+        super()._check(x)
         KD.folded_len(x.shape[2], self.period)
 
-    def _run(self, x, keep=False):
-        """-> (score, feats, state).  keep: also what the backward reads (the folded weights, the parameters' views, the input)."""
-        B, _, T = x.shape
-        p = self.period
-        with torch.no_grad():
-            x2 = x.detach().reshape(B, T).contiguous()
-            ops, bufs, state = {}, {}, {}
-            for e in self.launch_plan():
-                kind, layer = e["kind"], e["layer"]
-                if kind == "fold":
-                    v, g = self._leaf(layer).vg()
-                    first = layer == "convs.0"
-                    w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=first or (keep and e["mode"] == 0), want_op=not first)
-                    ops[layer] = (w32, op, self._leaf(layer).bias.detach().contiguous(), v, g)
-                    continue
-                w32, op, bias = ops[layer][:3]
-                if kind == "input":
-                    bufs[e["dst"]] = KD.disc_input(x2, w32, bias, p, slope=LRELU_SLOPE)
-                elif kind == "conv":
-                    bufs[e["dst"]] = KD.disc_conv(bufs[e["src"]], op, bias, e["cout"], e["stride"], slope=LRELU_SLOPE)
-                else:
-                    src = bufs[e["src"]]
-                    bufs[e["dst"]] = KD.disc_post(src, op, bias).view(B, src.shape[1], p, 1)
-            n = len(STRIDES)
-            feats = [bufs[j].permute(0, 3, 1, 2) for j in range(n + 1)]
-            score = bufs[n].view(B, -1)
-            if keep:
-                state = dict(ops=ops, bufs=bufs, x=x2, T=T)
-        return score, feats, state
+    def _four(self, t):
+        return t
 
-    def _backward(self, state, gscore, gfeats, need_dx, need_params):
-        """(dx or None, the 18 parameter gradients in named_parameters() order or Nones) from whichever of the seven output gradients
-        arrived: executes backward_plan()."""
-        ops, bufs, x2, T = state["ops"], state["bufs"], state["x"], state["T"]
-        p, n = self.period, len(STRIDES)
-        B = x2.shape[0]
+    _stored = _four
 
-        def channel_last(g):
-            """a (B, C, L, p) gradient as contiguous (B, L, p, C): in place when it already is channel-last-strided, else one copy"""
-            if g is None:
-                return None
-            g = g.detach().float().permute(0, 2, 3, 1)
-            return g if g.is_contiguous() else g.contiguous()
+    def _do_input(self, c, e):
+        o = c.ops[e["layer"]]
+        c.bufs[e["dst"]] = KD.disc_input(c.x, o.w32, o.bias, self.period, slope=LRELU_SLOPE)
 
-        def flat(g):
-            return None if g is None else g.detach().float().reshape(B, -1).contiguous()
+    def _do_input_wgrad(self, c, e):
+        c.parts = KD.disc_input_wgrad(c.dpre, c.x, self.period)
 
-        gf = [channel_last(g) for g in gfeats[:n]]
-        out, parts, dpre, opT, dx = {}, None, None, None, None
-        with torch.no_grad():
-            for e in self.backward_plan(need_dx, need_params):
-                kind, layer = e["kind"], e["layer"]
-                w32, op, _, v, g = ops[layer]
-                if kind == "post_bwd":
-                    dpre, wp, bp = KD.disc_post_bwd(bufs[e["src"]], op, dy1=flat(gscore), dy2=flat(gfeats[n]), add=gf[e["src"]], slope=LRELU_SLOPE)
-                    parts = (wp, bp)
-                elif kind == "wgrad":
-                    parts = KD.disc_wgrad(dpre, bufs[e["src"]], e["stride"])
-                elif kind == "input_wgrad":
-                    parts = KD.disc_input_wgrad(dpre, x2, p)
-                elif kind == "finish":
-                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], v, g)
-                    parts = None
-                elif kind == "fold_bwd":
-                    opT = KV.hifigan_fold_bwd(0, w32, torch.float32)
-                elif kind == "dgrad":
-                    mask = bufs[e["mask"]]
-                    dpre = KD.disc_dgrad(dpre, opT, mask.shape[1], e["cin"], e["stride"], mask_src=mask, add=gf[e["mask"]], slope=LRELU_SLOPE)
-                    opT = None
-                else:
-                    dx = KD.disc_input_dgrad(dpre, w32, T, p).view(B, 1, T)
-        grads = []
-        for name, prm in self.named_parameters():
-            if not need_params:
-                grads.append(None)
-                continue
-            layer, leaf = name.rsplit(".", 1)
-            gw, gg, gb = out[layer]
-            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
-        return dx, grads
+    def _do_input_dgrad(self, c, e):
+        B, T = c.x.shape
+        c.dx = KD.disc_input_dgrad(c.dpre, c.ops[e["layer"]].w32, T, self.period).view(B, 1, T)
 
-    def forward(self, x):
-        self._check(x)
-        params = [prm for _, prm in self.named_parameters()]
-        if torch.is_grad_enabled() and (x.requires_grad or any(prm.requires_grad for prm in params)):
-            res = _PeriodFunction.apply(self, x, *params)
-            return res[0], list(res[1:])
-        score, feats, _ = self._run(x)
-        return score, feats
+    _HANDLERS = dict(_Discriminator._HANDLERS, input=_do_input, input_wgrad=_do_input_wgrad, input_dgrad=_do_input_dgrad)
 
 
 class MultiPeriodDiscriminator(nn.Module):
@@ -284,18 +352,6 @@ def scale_lengths(T):
     return out + [L]
 
 
-class _WNConv1d(nn.Module):
-    """Parameters of weight_norm(Conv1d(cin, cout, k, groups=groups)) in the reference's checkpoint form, torch's default initialisation."""
-
-    def __init__(self, cin, cout, k, groups=1):
-        super().__init__()
-        bound = 1.0 / math.sqrt(cin // groups * k)
-        v = torch.empty(cout, cin // groups, k).uniform_(-bound, bound)
-        self.bias = nn.Parameter(torch.empty(cout).uniform_(-bound, bound))
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
-        self.weight_v = nn.Parameter(v)
-
-
 class _SNConv1d(nn.Module):
     """Parameters and buffers of torch.nn.utils.spectral_norm(Conv1d(cin, cout, k, groups=groups)) (the hook form: dim 0, one power
     iteration, eps 1e-12) in the reference's checkpoint form; u and v are normalised normal draws."""
@@ -307,26 +363,6 @@ class _SNConv1d(nn.Module):
         self.weight_orig = nn.Parameter(torch.empty(cout, cin // groups, k).uniform_(-bound, bound))
         self.register_buffer("weight_u", torch.nn.functional.normalize(torch.randn(cout), dim=0, eps=KM.SN_EPS))
         self.register_buffer("weight_v", torch.nn.functional.normalize(torch.randn(cin // groups * k), dim=0, eps=KM.SN_EPS))
-
-
-class _ScaleFunction(torch.autograd.Function):
-    """One ScaleDiscriminator call as ONE autograd node: inputs x and the 16 or 24 parameters, outputs the score and the eight features."""
-
-    @staticmethod
-    def forward(ctx, disc, x, *params):
-        ctx.set_materialize_grads(False)
-        score, feats, state = disc._run(x, keep=True)
-        ctx.disc, ctx.state = disc, state
-        ctx.save_for_backward(*params)           # autograd refuses a backward after an in-place update of one of them
-        return (score,) + tuple(feats)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gscore, *gfeats):
-        ctx.saved_tensors                        # the version check of the parameters
-        need_dx, need_params = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
-        dx, grads = ctx.disc._backward(ctx.state, gscore, gfeats, need_dx, need_params)
-        return (None, dx) + tuple(grads)
 
 
 class _PoolFunction(torch.autograd.Function):
@@ -352,14 +388,20 @@ class _MeanPool(nn.Module):
         return _PoolFunction.apply(x)
 
 
-class ScaleDiscriminator(nn.Module):
+class ScaleDiscriminator(_Discriminator):
     """HiFi-GAN scale discriminator (reference urhythmic/vocoder.py:330-365).  x (B, 1, T) fp32 on the device ->
     (score (B, L), [eight features (B, C, L)])."""
+    _FUNCTION = _ScaleFunction
+    _TO_CALLER = _FROM_CALLER = (0, 2, 1)
+    _MIN_T = 1
 
     def __init__(self, use_spectral_norm=False):
         super().__init__()
         self.use_spectral_norm = bool(use_spectral_norm)
-        leaf = _SNConv1d if self.use_spectral_norm else _WNConv1d
+
+        def leaf(cin, cout, k, groups=1):
+            return _SNConv1d(cin, cout, k, groups) if self.use_spectral_norm else _WNConv((cout, cin // groups, k))
+
         self.convs = nn.ModuleList([leaf(cin, cout, k, g) for cin, cout, k, _, g in MSD_LAYERS[:-1]])
         self.conv_post = leaf(*MSD_LAYERS[-1][:3])
 
@@ -408,143 +450,65 @@ class ScaleDiscriminator(nn.Module):
             plan.append(dict(kind="input_dgrad", layer="convs.0"))
         return plan
 
-    # ---- execution --------------------------------------------------------------------------------------------------------
-    def _leaf(self, name):
-        return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
+    # ---- execution: the buffers are (B, L, C); the shared launchers take them as (B, L, 1, C) ----------------------------------
+    def _four(self, t):
+        return None if t is None else t.unsqueeze(2)
 
-    def _check(self, x):
-        if x.dim() != 3 or x.shape[1] != 1 or x.shape[2] < 1:
-            raise ValueError(f"ScaleDiscriminator: x (B, 1, T) expected, got {tuple(x.shape)}")
-        dtypes = {x.dtype} | {p.dtype for p in self.parameters()} | {b.dtype for b in self.buffers()}
-        if torch.bfloat16 in dtypes or torch.float16 in dtypes:
-            raise NotImplementedError("ScaleDiscriminator runs in fp32 only: a 16-bit forward flips leaky-relu masks, which alone puts the "
-                                      "gradients several per cent off (DESIGN.md section 8)")
-        if dtypes != {torch.float32}:
-            raise TypeError("ScaleDiscriminator: float32 input and parameters")
-        if not x.is_cuda or not self.conv_post.bias.is_cuda:
-            raise RuntimeError("ScaleDiscriminator needs GPU tensors and GPU parameters (there is no CPU path)")
+    def _stored(self, t):
+        return t.squeeze(2)
 
-    def _run(self, x, keep=False):
-        """-> (score, feats, state).  keep: also what the backward reads (the folded weights, the parameters' views, the input, and
-        copies of the u, v, sigma this call used)."""
-        B, _, T = x.shape
-        with torch.no_grad():
-            x2 = x.detach().reshape(B, T).contiguous()
-            ops, bufs, state = {}, {}, {}
-            for e in self.launch_plan():
-                kind, layer = e["kind"], e["layer"]
-                leaf = self._leaf(layer)
-                if kind == "sn_power":
-                    W = leaf.weight_orig.detach().contiguous()
-                    sigma = KM.msd_sn_power(W, leaf.weight_u, leaf.weight_v, e["iterate"])
-                    ops[layer] = dict(v=W, g=None, bias=leaf.bias.detach().contiguous(), sigma=sigma,
-                                      uv=(leaf.weight_u.clone(), leaf.weight_v.clone()) if keep else None)
-                    continue
-                if kind == "sn_scale":
-                    ops[layer]["w32"] = KM.msd_sn_scale(ops[layer]["v"], ops[layer]["sigma"])
-                    continue
-                if kind == "fold":
-                    if self.use_spectral_norm:
-                        o = ops[layer]
-                        o["op"] = KV.hifigan_fold(e["mode"], o["w32"], None, torch.float32, want_w32=False)[1]
-                    else:
-                        v, g = leaf.weight_v.detach().contiguous(), leaf.weight_g.detach().contiguous().view(-1)
-                        w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=not e["op"] or (keep and e["mode"] == 0), want_op=e["op"])
-                        ops[layer] = dict(v=v, g=g, bias=leaf.bias.detach().contiguous(), w32=w32, op=op)
-                    continue
-                o = ops[layer]
-                if kind == "input":
-                    bufs[e["dst"]] = KM.msd_input(x2, o["w32"], o["bias"], slope=LRELU_SLOPE)
-                elif kind == "gconv":
-                    bufs[e["dst"]] = KM.msd_gconv(bufs[e["src"]], o["op"], o["bias"], e["cout"], e["groups"], e["stride"], slope=LRELU_SLOPE)
-                elif kind == "conv":
-                    bufs[e["dst"]] = KD.disc_conv(bufs[e["src"]].unsqueeze(2), o["op"], o["bias"], e["cout"], e["stride"], slope=LRELU_SLOPE).squeeze(2)
-                else:
-                    src = bufs[e["src"]]
-                    bufs[e["dst"]] = KD.disc_post(src.unsqueeze(2), o["op"], o["bias"]).view(B, src.shape[1], 1)
-            n = len(MSD_LAYERS) - 1
-            feats = [bufs[j].permute(0, 2, 1) for j in range(n + 1)]
-            score = bufs[n].view(B, -1)
-            if keep:
-                state = dict(ops=ops, bufs=bufs, x=x2)
-        return score, feats, state
+    def _do_sn_power(self, c, e):
+        leaf = self._leaf(e["layer"])
+        W = leaf.weight_orig.detach().contiguous()
+        sigma = KM.msd_sn_power(W, leaf.weight_u, leaf.weight_v, e["iterate"])
+        c.ops[e["layer"]] = _Layer(W, None, leaf.bias.detach().contiguous(), sigma=sigma,
+                                   uv=(leaf.weight_u.clone(), leaf.weight_v.clone()) if c.keep else None)
 
-    def _backward(self, state, gscore, gfeats, need_dx, need_params):
-        """(dx or None, the parameter gradients in named_parameters() order or Nones) from whichever of the nine output gradients
-        arrived: executes backward_plan()."""
-        ops, bufs, x2 = state["ops"], state["bufs"], state["x"]
-        n = len(MSD_LAYERS) - 1
-        B, T = x2.shape
+    def _do_sn_scale(self, c, e):
+        o = c.ops[e["layer"]]
+        o.w32 = KM.msd_sn_scale(o.v, o.sigma)
 
-        def channel_last(g):
-            """a (B, C, L) gradient as contiguous (B, L, C): in place when it already is channel-last-strided, else one copy"""
-            if g is None:
-                return None
-            g = g.detach().float().permute(0, 2, 1)
-            return g if g.is_contiguous() else g.contiguous()
+    def _do_fold(self, c, e):
+        if not self.use_spectral_norm:
+            return super()._do_fold(c, e)
+        o = c.ops[e["layer"]]
+        o.op = KV.hifigan_fold(e["mode"], o.w32, None, torch.float32, want_w32=False)[1]
 
-        def flat(g):
-            return None if g is None else g.detach().float().reshape(B, -1).contiguous()
+    def _do_input(self, c, e):
+        o = c.ops[e["layer"]]
+        c.bufs[e["dst"]] = KM.msd_input(c.x, o.w32, o.bias, slope=LRELU_SLOPE)
 
-        def four(t):
-            return None if t is None else t.unsqueeze(2)
+    def _do_gconv(self, c, e):
+        o = c.ops[e["layer"]]
+        c.bufs[e["dst"]] = KM.msd_gconv(c.bufs[e["src"]], o.op, o.bias, e["cout"], e["groups"], e["stride"], slope=LRELU_SLOPE)
 
-        gf = [channel_last(g) for g in gfeats[:n]]
-        out, parts, dpre, opT, dx = {}, None, None, None, None
-        with torch.no_grad():
-            for e in self.backward_plan(need_dx, need_params):
-                kind, layer = e["kind"], e["layer"]
-                o = ops[layer]
-                if kind == "post_bwd":
-                    dpre, wp, bp = KD.disc_post_bwd(four(bufs[e["src"]]), o["op"], dy1=flat(gscore), dy2=flat(gfeats[n]), add=four(gf[e["src"]]),
-                                                    slope=LRELU_SLOPE)
-                    dpre, parts = dpre.squeeze(2), (wp, bp)
-                elif kind == "wgrad":
-                    parts = KD.disc_wgrad(four(dpre), four(bufs[e["src"]]), e["stride"])
-                elif kind == "gconv_wgrad":
-                    parts = KM.msd_gconv_wgrad(dpre, bufs[e["src"]], e["groups"], e["stride"])
-                elif kind == "input_wgrad":
-                    parts = KM.msd_input_wgrad(dpre, x2)
-                elif kind == "finish":
-                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], o["v"], o["g"])
-                    parts = None
-                elif kind == "sn_finish":
-                    gw, _, gb = out[layer]
-                    out[layer] = (KM.msd_sn_finish(gw, o["v"], o["uv"][0], o["uv"][1], o["sigma"]), None, gb)
-                elif kind == "fold_bwd":
-                    opT = KV.hifigan_fold_bwd(0, o["w32"], torch.float32)
-                elif kind == "gfold_bwd":
-                    opT = KM.msd_fold_bwd(o["w32"], e["groups"])
-                elif kind == "dgrad":
-                    mask = bufs[e["mask"]]
-                    dpre = KD.disc_dgrad(four(dpre), opT, mask.shape[1], e["cin"], e["stride"], mask_src=four(mask), add=four(gf[e["mask"]]),
-                                         slope=LRELU_SLOPE).squeeze(2)
-                    opT = None
-                elif kind == "gconv_dgrad":
-                    mask = bufs[e["mask"]]
-                    dpre = KM.msd_gconv_dgrad(dpre, opT, mask.shape[1], e["cin"], e["groups"], e["stride"], mask_src=mask, add=gf[e["mask"]],
-                                              slope=LRELU_SLOPE)
-                    opT = None
-                else:
-                    dx = KM.msd_input_dgrad(dpre, o["w32"]).view(B, 1, T)
-        grads = []
-        for name, prm in self.named_parameters():
-            if not need_params:
-                grads.append(None)
-                continue
-            layer, leaf = name.rsplit(".", 1)
-            gw, gg, gb = out[layer]
-            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
-        return dx, grads
+    def _do_gconv_wgrad(self, c, e):
+        c.parts = KM.msd_gconv_wgrad(c.dpre, c.bufs[e["src"]], e["groups"], e["stride"])
 
-    def forward(self, x):
-        self._check(x)
-        params = [prm for _, prm in self.named_parameters()]
-        if torch.is_grad_enabled() and (x.requires_grad or any(prm.requires_grad for prm in params)):
-            res = _ScaleFunction.apply(self, x, *params)
-            return res[0], list(res[1:])
-        score, feats, _ = self._run(x)
-        return score, feats
+    def _do_input_wgrad(self, c, e):
+        c.parts = KM.msd_input_wgrad(c.dpre, c.x)
+
+    def _do_sn_finish(self, c, e):
+        o = c.ops[e["layer"]]
+        gw, _, gb = c.out[e["layer"]]
+        c.out[e["layer"]] = (KM.msd_sn_finish(gw, o.v, o.uv[0], o.uv[1], o.sigma), None, gb)
+
+    def _do_gfold_bwd(self, c, e):
+        c.opT = KM.msd_fold_bwd(c.ops[e["layer"]].w32, e["groups"])
+
+    def _do_gconv_dgrad(self, c, e):
+        mask = c.bufs[e["mask"]]
+        c.dpre = KM.msd_gconv_dgrad(c.dpre, c.opT, mask.shape[1], e["cin"], e["groups"], e["stride"], mask_src=mask, add=c.gf[e["mask"]],
+                                    slope=LRELU_SLOPE)
+        c.opT = None
+
+    def _do_input_dgrad(self, c, e):
+        B, T = c.x.shape
+        c.dx = KM.msd_input_dgrad(c.dpre, c.ops[e["layer"]].w32).view(B, 1, T)
+
+    _HANDLERS = dict(_Discriminator._HANDLERS, sn_power=_do_sn_power, sn_scale=_do_sn_scale, fold=_do_fold, input=_do_input, gconv=_do_gconv,
+                     gconv_wgrad=_do_gconv_wgrad, input_wgrad=_do_input_wgrad, sn_finish=_do_sn_finish, gfold_bwd=_do_gfold_bwd,
+                     gconv_dgrad=_do_gconv_dgrad, input_dgrad=_do_input_dgrad)
 
 
 class MultiScaleDiscriminator(nn.Module):

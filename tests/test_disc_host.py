@@ -205,3 +205,16 @@ def test_header_sigs_exports_and_sources():
         assert "replaces:" in header[header.rindex("/*", 0, decl):decl], n
     src = open(os.path.join(_lib.CSRC, "hifigan_disc.hip")).read()
     assert "atomic" not in src.replace("no atomics", "") and all(('extern "C" int ' + n + "(") in src for n in names)
+
+
+def test_both_halves_share_one_node_body_and_one_handler_table():
+    from seq2seq_vc_amd.urhythmic import vocoder as V
+    assert V._PeriodFunction.__mro__[1] is V._ScaleFunction.__mro__[1] is V._DiscFunction
+    assert "forward" not in vars(V._PeriodFunction) and "backward" not in vars(V._ScaleFunction)
+    assert issubclass(V.PeriodDiscriminator, V._Discriminator) and issubclass(V.ScaleDiscriminator, V._Discriminator)
+    assert set(V.PeriodDiscriminator._HANDLERS) == set(V.KINDS) | set(V.BWD_KINDS)
+    assert set(V.ScaleDiscriminator._HANDLERS) == set(V.MSD_KINDS) | set(V.MSD_BWD_KINDS)
+    shared = ("fold", "conv", "post", "post_bwd", "wgrad", "finish", "fold_bwd", "dgrad")
+    assert set(V._Discriminator._HANDLERS) == set(shared)
+    for kind in shared[1:]:                       # the scale half folds a spectrally normed weight itself
+        assert V.PeriodDiscriminator._HANDLERS[kind] is V.ScaleDiscriminator._HANDLERS[kind] is V._Discriminator._HANDLERS[kind], kind
