@@ -17,7 +17,9 @@ of the spectrally normed scale still happens (four per step in train() mode).  T
 weight_u / weight_v buffers and the three losses have the same bits in both modes; the ONLY observable difference is what the
 discriminator's .grad holds after the step (lean: the gradients of the discriminator loss that its optimiser consumed).
 
-`launch_plan()` lists the library launches of one step per stage; step() executes exactly that list.  What is still ATen inside a
+`launch_plan()` lists the library launches of one step per stage: the concatenation of what the nets themselves say a forward or a
+backward of theirs calls (`HifiganGenerator.calls`, `HifiganDiscriminator.calls`; vocoder/plan.py) under this step's stage labels,
+plus the loss and optimiser launches of its own; step() executes exactly that list.  What is still ATen inside a
 step, in both modes: the scalar combination 45 loss_mel + 2 loss_features + loss_adversarial with its backward, autograd's sums of the
 data gradients that meet at wavs_ (and at the pooled inputs of the scales), and -- in reference mode only -- the accumulation into
 the discriminator's .grad.  Out of scope: graph capture of the step, DDP, one B = 16 discriminator call for real and generated (it
@@ -35,40 +37,6 @@ from .vocoder import HifiganDiscriminator, discriminator_loss, feature_loss, gen
 
 MODES = ("lean", "reference")
 MEL_WEIGHT, FEATURE_WEIGHT = 45, 2
-# plan kind -> the library calls its launcher makes ("fold" / "fold_bwd" zero-fill the operand buffer they lay out with one more call)
-_CALLS = {
-    "input": ("hifigan_input",), "conv1d": ("hifigan_conv1d",), "tconv1d": ("hifigan_tconv1d",), "conv_out": ("hifigan_conv_out",),
-    "conv_out_bwd": ("hifigan_conv_out_bwd",), "gen_wgrad": ("hifigan_wgrad",), "finish": ("hifigan_wgrad_finish",),
-    "tconv1d_dgrad": ("hifigan_tconv1d_dgrad",), "conv1d_dgrad": ("hifigan_conv1d_dgrad",),
-    "fold_op": ("fill_zero", "hifigan_fold"), "fold_w32": ("hifigan_fold",), "fold_bwd": ("fill_zero", "hifigan_fold_bwd"),
-    "disc_input": ("hifigan_disc_input",), "conv": ("hifigan_disc_conv",), "post": ("hifigan_disc_post",),
-    "post_bwd": ("hifigan_disc_post_bwd",), "wgrad": ("hifigan_disc_wgrad",), "disc_input_wgrad": ("hifigan_disc_input_wgrad",),
-    "dgrad": ("hifigan_disc_dgrad",), "disc_input_dgrad": ("hifigan_disc_input_dgrad",),
-    "sn_power": ("hifigan_msd_sn_power",), "sn_scale": ("hifigan_msd_sn_scale",), "msd_input": ("hifigan_msd_input",),
-    "gconv": ("hifigan_msd_gconv",), "pool": ("hifigan_msd_pool",), "pool_bwd": ("hifigan_msd_pool_bwd",),
-    "gconv_wgrad": ("hifigan_msd_gconv_wgrad",), "msd_input_wgrad": ("hifigan_msd_input_wgrad",), "sn_finish": ("hifigan_msd_sn_finish",),
-    "gfold_bwd": ("hifigan_msd_fold_bwd",), "gconv_dgrad": ("hifigan_msd_gconv_dgrad",), "msd_input_dgrad": ("hifigan_msd_input_dgrad",),
-}
-
-
-def _expand(stage, entries, scale_net=False, generator=False):
-    """Plan entries of a net -> one dict per library call, `call` being the name the launcher reports."""
-    out = []
-    for e in entries:
-        kind = e["kind"]
-        if kind == "fold":
-            # the input layers need the folded weight alone; every other layer an operand buffer, zero-filled first
-            first = e.get("layer") == "convs.0" and not generator
-            if scale_net and "op" in e:
-                first = not e["op"]
-            kind = "fold_w32" if first else "fold_op"
-        elif generator and kind == "wgrad":
-            kind = "gen_wgrad"
-        elif kind in ("input", "input_wgrad", "input_dgrad") and not generator:
-            kind = ("msd_" if scale_net else "disc_") + kind
-        for call in _CALLS[kind]:
-            out.append(dict(e, stage=stage, call=call))
-    return out
 
 
 class VocoderFineTuner:
@@ -103,65 +71,33 @@ class VocoderFineTuner:
         self.scheduler_discriminator = torch.optim.lr_scheduler.ExponentialLR(self.optimizer_discriminator, gamma=lr_decay)
 
     # ---- the launch list ----------------------------------------------------------------------------------------------------
-    def _generator_plan(self):
-        G = self.generator
-        fwd = []
-        for name, _ in G._leaves():                       # _forward_train: fold every layer, lay out the data gradient's operand
-            mode, _ = G._layer_mode(name)
-            fwd.append(dict(kind="fold", layer=name))
-            if mode != 2 and name != "conv_pre":
-                fwd.append(dict(kind="fold_bwd", layer=name))
-        return _expand("generator forward", fwd + G._train_plan(), generator=True), G.backward_plan()
-
-    def _discriminator_forward(self, stage):
-        D = self.discriminator
-        out = []
-        for d in D.mpd.discriminators:
-            out += _expand(stage, [dict(e, period=d.period) for e in d.launch_plan()])
-        for i, d in enumerate(D.msd.discriminators):
-            out += _expand(stage, ([dict(kind="pool", scale=i)] if i else []) + [dict(e, scale=i) for e in d.launch_plan()], scale_net=True)
-        return out
-
-    def _discriminator_backward(self, stage, need_dx, need_params):
-        """In the order autograd runs the nodes of one call: the last one made first."""
-        D = self.discriminator
-        out = []
-        scales = list(enumerate(D.msd.discriminators))
-        for i, d in reversed(scales):
-            out += _expand(stage, [dict(e, scale=i) for e in d.backward_plan(need_dx, need_params)] +
-                           ([dict(kind="pool_bwd", scale=i)] if need_dx and i else []), scale_net=True)
-        for d in reversed(list(D.mpd.discriminators)):
-            out += _expand(stage, [dict(e, period=d.period) for e in d.backward_plan(need_dx, need_params)])
-        return out
-
     def launch_plan(self):
         """The library launches of one step(), in order, one dict per call into the library: `stage`, `call` (the entry point's name
         without the prefix) and the fields of the net's own plan entry it came from.  step() executes exactly this list (within one
         backward stage the order of the sub-discriminators' nodes is autograd's: the last one made first)."""
-        lean = self.mode == "lean"
-        gen_fwd, gen_bwd = self._generator_plan()
+        G, D, lean = self.generator, self.discriminator, self.mode == "lean"
 
         def own(stage, *calls):
             return [dict(stage=stage, kind="loss" if "loss" in c else "optimizer", call=c) for c in calls]
 
-        plan = list(gen_fwd)
-        plan += self._discriminator_forward("discriminator half: D(wavs)")
-        plan += self._discriminator_forward("discriminator half: D(wavs_.detach())")
+        plan = G.calls(G.train_plan(torch.float32), "generator forward")
+        plan += D.calls("discriminator half: D(wavs)")
+        plan += D.calls("discriminator half: D(wavs_.detach())")
         plan += own("discriminator half: discriminator_loss", "gan_score_loss")
         plan += own("discriminator half: backward", "gan_score_loss_bwd")
-        plan += self._discriminator_backward("discriminator half: backward of D(wavs_.detach())", False, True)
-        plan += self._discriminator_backward("discriminator half: backward of D(wavs)", False, True)
+        plan += D.calls("discriminator half: backward of D(wavs_.detach())", (False, True))
+        plan += D.calls("discriminator half: backward of D(wavs)", (False, True))
         plan += own("discriminator half: optimizer_discriminator.step", *["adamw_multi"] * self.optimizer_discriminator.launches_per_step())
-        plan += self._discriminator_forward("generator half: D(wavs)" + (" under no_grad" if lean else ""))
-        plan += self._discriminator_forward("generator half: D(wavs_)" + (" with frozen parameters" if lean else ""))
+        plan += D.calls("generator half: D(wavs)" + (" under no_grad" if lean else ""))
+        plan += D.calls("generator half: D(wavs_)" + (" with frozen parameters" if lean else ""))
         plan += own("generator half: mel l1_loss", "melspec_fwd", "melspec_loss_finish")
         plan += own("generator half: feature_loss", "gan_feature_loss")
         plan += own("generator half: generator_loss", "gan_score_loss")
         plan += own("generator half: backward", "gan_score_loss_bwd", "gan_feature_loss_bwd", "melspec_bwd_frames", "melspec_bwd_ola")
-        plan += self._discriminator_backward("generator half: backward of D(wavs_)", True, not lean)
+        plan += D.calls("generator half: backward of D(wavs_)", (True, not lean))
         if not lean:
-            plan += self._discriminator_backward("generator half: backward of D(wavs)", False, True)
-        plan += _expand("generator half: backward of the generator", gen_bwd, generator=True)
+            plan += D.calls("generator half: backward of D(wavs)", (False, True))
+        plan += G.calls(G.backward_plan(), "generator half: backward of the generator")
         plan += own("generator half: optimizer_generator.step", *["adamw_multi"] * self.optimizer_generator.launches_per_step())
         return plan
 

@@ -10,12 +10,14 @@ discriminator, or its `mpd.*` / `msd.*` subtree, loads as it is.  The three loss
 of this file, one autograd node and one table-driven launch sequence each (csrc/gan_loss.hip); the optimiser is optim.MultiAdamW and
 the whole loop body is urhythmic/fine_tune.py.
 
-PeriodDiscriminator and ScaleDiscriminator are one executor, `_Discriminator`: `launch_plan()` / `backward_plan()` list the launches
-of one call as dicts, and the forward and the backward walk that list through one table from `kind` to handler.  The launches both
-halves share (the weight-norm fold, the 5-tap convolution, conv_post, their backward) have one handler each, written for the period
-half's 4-D buffers; a class says how its stored buffers become that view (`_four` / `_stored`: the identity there, `unsqueeze(2)` /
-`squeeze(2)` in the scale half, whose layer 6 and conv_post are the period kernels at p = 1) and registers the kinds it has alone.
-The lists are built once per module and mode (`_plan`): a call walks the stored list.
+PeriodDiscriminator and ScaleDiscriminator are one executor, `_Discriminator`, over vocoder/plan.py (the weight-norm leaf, the
+cached lists, the walk through one table from `kind` to handler, `calls()`), which the generator runs on too: `launch_plan()` /
+`backward_plan()` list the launches of one call as dicts, built once per module and mode.  The launches both halves share (the
+weight-norm fold, the 5-tap convolution, conv_post, their backward) have one handler each, written for the period half's 4-D
+buffers; a class says how its stored buffers become that view (`_four` / `_stored`: the identity there, `unsqueeze(2)` /
+`squeeze(2)` in the scale half, whose layer 6 and conv_post are the period kernels at p = 1) and defines the handlers of the kinds it
+has alone.  The three containers add `calls(stage, backward)`: the library calls of one forward or one backward of theirs, in the
+order they run, which is what urhythmic/fine_tune.py concatenates into the plan of a step.
 
 Activations are channel-last, (B, L, p, C) or (B, L, C); the features handed out are strided (B, C, L, p) / (B, C, L) views of them
 and the score is the flattening of the last one.  Under grad mode a call is ONE autograd node whose inputs are x and the parameters
@@ -36,6 +38,7 @@ from ..ops import kernels_disc as KD
 from ..ops import kernels_ganloss as KG
 from ..ops import kernels_msd as KM
 from ..ops import kernels_vocoder as KV
+from ..vocoder.plan import Layer, PlanExecutor, WNConv, fold_calls, handles
 
 LRELU_SLOPE = 0.1
 PERIODS = (2, 3, 5, 7, 11)
@@ -45,38 +48,12 @@ KINDS = ("fold", "input", "conv", "post")
 BWD_KINDS = ("post_bwd", "wgrad", "input_wgrad", "finish", "fold_bwd", "dgrad", "input_dgrad")
 
 
-class _WNConv(nn.Module):
-    """Parameters of a weight-normed convolution in the reference's checkpoint form, torch's default initialisation: `shape` is
-    (O, C, k, 1) for weight_norm(Conv2d(C, O, (k, 1))) and (O, C / groups, k) for weight_norm(Conv1d(C, O, k, groups=groups))."""
-
-    def __init__(self, shape):
-        super().__init__()
-        bound = 1.0 / math.sqrt(shape[1] * shape[2])
-        v = torch.empty(*shape).uniform_(-bound, bound)
-        self.bias = nn.Parameter(torch.empty(shape[0]).uniform_(-bound, bound))
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, *[1] * (len(shape) - 1)))
-        self.weight_v = nn.Parameter(v)
-
-    def vg(self):
-        """(v (O, C, k), g (O)) fp32 contiguous views of the live parameters"""
-        return self.weight_v.detach().contiguous().flatten(2), self.weight_g.detach().contiguous().view(-1)
-
-
 def layer_lengths(T, p):
     """[L0, L1, .., L5]: rows along L of the folded input and of the output of convs[0..4] (conv_post keeps L5)."""
     L = [KD.folded_len(T, p)[0]]
     for s in STRIDES:
         L.append(KD.out_len(L[-1], s))
     return L
-
-
-class _Layer:
-    """What one call holds of a layer: v, g = the parameters' views (v = weight_orig and g = None under spectral norm), bias, w32 =
-    the folded weight, op = the GEMM operand, and under spectral norm sigma and uv = copies of the u, v the call used."""
-    __slots__ = ("v", "g", "bias", "w32", "op", "sigma", "uv")
-
-    def __init__(self, v, g, bias, w32=None, op=None, sigma=None, uv=None):
-        self.v, self.g, self.bias, self.w32, self.op, self.sigma, self.uv = v, g, bias, w32, op, sigma, uv
 
 
 class _DiscFunction(torch.autograd.Function):
@@ -111,21 +88,13 @@ def _flat(g, B):
     return None if g is None else g.detach().float().reshape(B, -1).contiguous()
 
 
-class _Discriminator(nn.Module):
+class _Discriminator(PlanExecutor):
     """The executor of both discriminator halves.  A subclass has `convs`, `conv_post`, `launch_plan()` and `backward_plan()`, names
     its autograd node (`_FUNCTION`), the permutations between its stored buffers and the caller's features (`_TO_CALLER`,
-    `_FROM_CALLER`), `_four` / `_stored`, and extends `_HANDLERS` by the kinds of its own.  A handler is `f(self, c, e)`: c = the
-    state of the call (ops: layer -> _Layer, bufs: index -> stored activation, x (B, T), keep; in the backward also gf = the features'
+    `_FROM_CALLER`), `_four` / `_stored`, and defines the `@handles` methods of the kinds of its own.  A handler is `f(self, c, e)`: c = the
+    state of the call (ops: layer -> Layer, bufs: index -> stored activation, x (B, T), keep; in the backward also gf = the features'
     gradients channel-last, gscore, glast, out: layer -> (gw, gg, gb), and parts, dpre, opT, dx = what one launch hands the next)."""
     _MIN_T = 0
-
-    def _plan(self, *flags):
-        """launch_plan() or, with (need_dx, need_params), backward_plan(): built once per train() / eval() mode and flags"""
-        key = (self.training,) + flags
-        plans = self.__dict__.setdefault("_plans", {})
-        if key not in plans:
-            plans[key] = self.backward_plan(*flags) if flags else self.launch_plan()
-        return plans[key]
 
     def _leaf(self, name):
         return self.conv_post if name == "conv_post" else self.convs[int(name.split(".")[1])]
@@ -149,8 +118,7 @@ class _Discriminator(nn.Module):
         B, _, T = x.shape
         with torch.no_grad():
             c = SimpleNamespace(ops={}, bufs={}, x=x.detach().reshape(B, T).contiguous(), keep=keep)
-            for e in self._plan():
-                self._HANDLERS[e["kind"]](self, c, e)
+            self._walk(self._plan("launch_plan"), c)
             n = len(self.convs)
             feats = [c.bufs[j].permute(*self._TO_CALLER) for j in range(n + 1)]
             score = c.bufs[n].view(B, -1)
@@ -170,18 +138,8 @@ class _Discriminator(nn.Module):
 
         c = SimpleNamespace(ops=state.ops, bufs=state.bufs, x=state.x, gf=[channel_last(g) for g in gfeats[:n]], gscore=gscore,
                             glast=gfeats[n], out={}, parts=None, dpre=None, opT=None, dx=None)
-        with torch.no_grad():
-            for e in self._plan(bool(need_dx), bool(need_params)):
-                self._HANDLERS[e["kind"]](self, c, e)
-        grads = []
-        for name, prm in self.named_parameters():
-            if not need_params:
-                grads.append(None)
-                continue
-            layer, leaf = name.rsplit(".", 1)
-            gw, gg, gb = c.out[layer]
-            grads.append((gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)).view_as(prm))
-        return c.dx, grads
+        self._walk(self._plan("backward_plan", bool(need_dx), bool(need_params)), c)
+        return c.dx, self._param_grads(c.out) if need_params else [None] * len(list(self.parameters()))
 
     def forward(self, x):
         self._check(x)
@@ -193,46 +151,44 @@ class _Discriminator(nn.Module):
         return score, feats
 
     # ---- the launches both halves have: the period half's launchers on the 4-D view of the buffers ---------------------------
+    @handles("fold", fold_calls)
     def _do_fold(self, c, e):
-        layer, leaf = e["layer"], self._leaf(e["layer"])
-        first = layer == "convs.0"                # the input layer reads the folded weight itself, the others the GEMM operand
-        v, g = leaf.vg()
-        w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=first or (c.keep and e["mode"] == 0), want_op=not first)
-        c.ops[layer] = _Layer(v, g, leaf.bias.detach().contiguous(), w32, op)
+        leaf = self._leaf(e["layer"])
+        v, g = leaf.vg()                          # the input layer reads the folded weight itself (`op` False), the others the operand
+        w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, want_w32=not e["op"] or (c.keep and e["mode"] == 0), want_op=e["op"])
+        c.ops[e["layer"]] = Layer(v, g, leaf.bias.detach().contiguous(), w32, op)
 
+    @handles("conv", "hifigan_disc_conv")
     def _do_conv(self, c, e):
         o = c.ops[e["layer"]]
         c.bufs[e["dst"]] = self._stored(KD.disc_conv(self._four(c.bufs[e["src"]]), o.op, o.bias, e["cout"], e["stride"], slope=LRELU_SLOPE))
 
+    @handles("post", "hifigan_disc_post")
     def _do_post(self, c, e):
         o, src = c.ops[e["layer"]], c.bufs[e["src"]]
         c.bufs[e["dst"]] = KD.disc_post(self._four(src), o.op, o.bias).view(src.shape[:-1] + (1,))
 
+    @handles("post_bwd", "hifigan_disc_post_bwd")
     def _do_post_bwd(self, c, e):
         B = c.x.shape[0]
         dpre, wp, bp = KD.disc_post_bwd(self._four(c.bufs[e["src"]]), c.ops[e["layer"]].op, dy1=_flat(c.gscore, B), dy2=_flat(c.glast, B),
                                         add=self._four(c.gf[e["src"]]), slope=LRELU_SLOPE)
         c.dpre, c.parts = self._stored(dpre), (wp, bp)
 
+    @handles("wgrad", "hifigan_disc_wgrad")
     def _do_wgrad(self, c, e):
         c.parts = KD.disc_wgrad(self._four(c.dpre), self._four(c.bufs[e["src"]]), e["stride"])
 
-    def _do_finish(self, c, e):
-        o = c.ops[e["layer"]]
-        c.out[e["layer"]] = KV.hifigan_wgrad_finish(e["mode"], c.parts[0], c.parts[1], o.v, o.g)
-        c.parts = None
-
+    @handles("fold_bwd", "fill_zero", "hifigan_fold_bwd")
     def _do_fold_bwd(self, c, e):
         c.opT = KV.hifigan_fold_bwd(0, c.ops[e["layer"]].w32, torch.float32)
 
+    @handles("dgrad", "hifigan_disc_dgrad")
     def _do_dgrad(self, c, e):
         mask = c.bufs[e["mask"]]
         c.dpre = self._stored(KD.disc_dgrad(self._four(c.dpre), c.opT, mask.shape[1], e["cin"], e["stride"], mask_src=self._four(mask),
                                             add=self._four(c.gf[e["mask"]]), slope=LRELU_SLOPE))
         c.opT = None
-
-    _HANDLERS = dict(fold=_do_fold, conv=_do_conv, post=_do_post, post_bwd=_do_post_bwd, wgrad=_do_wgrad, finish=_do_finish,
-                     fold_bwd=_do_fold_bwd, dgrad=_do_dgrad)
 
 
 class PeriodDiscriminator(_Discriminator):
@@ -250,15 +206,15 @@ class PeriodDiscriminator(_Discriminator):
         if int(period) < 1:
             raise ValueError("PeriodDiscriminator: period >= 1")
         self.period = int(period)
-        self.convs = nn.ModuleList([_WNConv((CHANNELS[j + 1], CHANNELS[j], kernel_size, 1)) for j in range(len(STRIDES))])
-        self.conv_post = _WNConv((1, CHANNELS[-1], KD.POST_TAPS, 1))
+        self.convs = nn.ModuleList([WNConv((CHANNELS[j + 1], CHANNELS[j], kernel_size, 1)) for j in range(len(STRIDES))])
+        self.conv_post = WNConv((1, CHANNELS[-1], KD.POST_TAPS, 1))
 
     # ---- the launch lists -------------------------------------------------------------------------------------------------
     def launch_plan(self):
         """What one forward call launches, in order: dicts with `kind` in KINDS: 12 per period, 60 per MultiPeriodDiscriminator call.
         forward() executes exactly this list.  ("fold" is the fold kernel; hifigan_fold zero-fills each of the five operand buffers with
         one more library launch beside it, and hifigan_fold_bwd does the same in the backward: 17 and 25 / 24 launches per period.)"""
-        plan = [dict(kind="fold", layer=f"convs.{j}", mode=0) for j in range(len(STRIDES))] + [dict(kind="fold", layer="conv_post", mode=2)]
+        plan = [dict(kind="fold", layer=f"convs.{j}", mode=0, op=j > 0) for j in range(len(STRIDES))] + [dict(kind="fold", layer="conv_post", mode=2, op=True)]
         plan.append(dict(kind="input", layer="convs.0", dst=0, cout=CHANNELS[1], stride=STRIDES[0]))
         for j in range(1, len(STRIDES)):
             plan.append(dict(kind="conv", layer=f"convs.{j}", src=j - 1, dst=j, cin=CHANNELS[j], cout=CHANNELS[j + 1], stride=STRIDES[j]))
@@ -295,18 +251,19 @@ class PeriodDiscriminator(_Discriminator):
 
     _stored = _four
 
+    @handles("input", "hifigan_disc_input")
     def _do_input(self, c, e):
         o = c.ops[e["layer"]]
         c.bufs[e["dst"]] = KD.disc_input(c.x, o.w32, o.bias, self.period, slope=LRELU_SLOPE)
 
+    @handles("input_wgrad", "hifigan_disc_input_wgrad")
     def _do_input_wgrad(self, c, e):
         c.parts = KD.disc_input_wgrad(c.dpre, c.x, self.period)
 
+    @handles("input_dgrad", "hifigan_disc_input_dgrad")
     def _do_input_dgrad(self, c, e):
         B, T = c.x.shape
         c.dx = KD.disc_input_dgrad(c.dpre, c.ops[e["layer"]].w32, T, self.period).view(B, 1, T)
-
-    _HANDLERS = dict(_Discriminator._HANDLERS, input=_do_input, input_wgrad=_do_input_wgrad, input_dgrad=_do_input_dgrad)
 
 
 class MultiPeriodDiscriminator(nn.Module):
@@ -322,6 +279,12 @@ class MultiPeriodDiscriminator(nn.Module):
 
     def backward_plan(self, need_dx=False, need_params=True):
         return [dict(e, period=d.period) for d in self.discriminators for e in d.backward_plan(need_dx, need_params)]
+
+    def calls(self, stage, backward=None):
+        """The library calls of one forward (PlanExecutor.calls of launch_plan()) or, with backward = (need_dx, need_params), of one
+        backward in the order autograd runs the nodes: the last one made first."""
+        ds = self.discriminators if backward is None else reversed(self.discriminators)
+        return [c for d in ds for c in d.calls([dict(e, period=d.period) for e in (d.backward_plan(*backward) if backward else d.launch_plan())], stage)]
 
     def forward(self, x):
         scores, feats = [], []
@@ -366,7 +329,8 @@ class _SNConv1d(nn.Module):
 
 
 class _PoolFunction(torch.autograd.Function):
-    """AvgPool1d(4, 2, padding=2) on (B, 1, T): the HIP forward and its adjoint."""
+    """AvgPool1d(4, 2, padding=2) on (B, 1, T): the HIP forward and its adjoint, one library call each (`CALLS`)."""
+    CALLS = ("hifigan_msd_pool", "hifigan_msd_pool_bwd")
 
     @staticmethod
     def forward(ctx, x):
@@ -400,7 +364,7 @@ class ScaleDiscriminator(_Discriminator):
         self.use_spectral_norm = bool(use_spectral_norm)
 
         def leaf(cin, cout, k, groups=1):
-            return _SNConv1d(cin, cout, k, groups) if self.use_spectral_norm else _WNConv((cout, cin // groups, k))
+            return _SNConv1d(cin, cout, k, groups) if self.use_spectral_norm else WNConv((cout, cin // groups, k))
 
         self.convs = nn.ModuleList([leaf(cin, cout, k, g) for cin, cout, k, _, g in MSD_LAYERS[:-1]])
         self.conv_post = leaf(*MSD_LAYERS[-1][:3])
@@ -457,58 +421,65 @@ class ScaleDiscriminator(_Discriminator):
     def _stored(self, t):
         return t.squeeze(2)
 
+    @handles("sn_power", "hifigan_msd_sn_power")
     def _do_sn_power(self, c, e):
         leaf = self._leaf(e["layer"])
         W = leaf.weight_orig.detach().contiguous()
         sigma = KM.msd_sn_power(W, leaf.weight_u, leaf.weight_v, e["iterate"])
-        c.ops[e["layer"]] = _Layer(W, None, leaf.bias.detach().contiguous(), sigma=sigma,
+        c.ops[e["layer"]] = Layer(W, None, leaf.bias.detach().contiguous(), sigma=sigma,
                                    uv=(leaf.weight_u.clone(), leaf.weight_v.clone()) if c.keep else None)
 
+    @handles("sn_scale", "hifigan_msd_sn_scale")
     def _do_sn_scale(self, c, e):
         o = c.ops[e["layer"]]
         o.w32 = KM.msd_sn_scale(o.v, o.sigma)
 
+    @handles("fold", fold_calls)
     def _do_fold(self, c, e):
         if not self.use_spectral_norm:
             return super()._do_fold(c, e)
         o = c.ops[e["layer"]]
         o.op = KV.hifigan_fold(e["mode"], o.w32, None, torch.float32, want_w32=False)[1]
 
+    @handles("input", "hifigan_msd_input")
     def _do_input(self, c, e):
         o = c.ops[e["layer"]]
         c.bufs[e["dst"]] = KM.msd_input(c.x, o.w32, o.bias, slope=LRELU_SLOPE)
 
+    @handles("gconv", "hifigan_msd_gconv")
     def _do_gconv(self, c, e):
         o = c.ops[e["layer"]]
         c.bufs[e["dst"]] = KM.msd_gconv(c.bufs[e["src"]], o.op, o.bias, e["cout"], e["groups"], e["stride"], slope=LRELU_SLOPE)
 
+    @handles("gconv_wgrad", "hifigan_msd_gconv_wgrad")
     def _do_gconv_wgrad(self, c, e):
         c.parts = KM.msd_gconv_wgrad(c.dpre, c.bufs[e["src"]], e["groups"], e["stride"])
 
+    @handles("input_wgrad", "hifigan_msd_input_wgrad")
     def _do_input_wgrad(self, c, e):
         c.parts = KM.msd_input_wgrad(c.dpre, c.x)
 
+    @handles("sn_finish", "hifigan_msd_sn_finish")
     def _do_sn_finish(self, c, e):
         o = c.ops[e["layer"]]
         gw, _, gb = c.out[e["layer"]]
         c.out[e["layer"]] = (KM.msd_sn_finish(gw, o.v, o.uv[0], o.uv[1], o.sigma), None, gb)
 
+    @handles("gfold_bwd", "hifigan_msd_fold_bwd")
     def _do_gfold_bwd(self, c, e):
         c.opT = KM.msd_fold_bwd(c.ops[e["layer"]].w32, e["groups"])
 
+    @handles("gconv_dgrad", "hifigan_msd_gconv_dgrad")
     def _do_gconv_dgrad(self, c, e):
         mask = c.bufs[e["mask"]]
         c.dpre = KM.msd_gconv_dgrad(c.dpre, c.opT, mask.shape[1], e["cin"], e["groups"], e["stride"], mask_src=mask, add=c.gf[e["mask"]],
                                     slope=LRELU_SLOPE)
         c.opT = None
 
+    @handles("input_dgrad", "hifigan_msd_input_dgrad")
     def _do_input_dgrad(self, c, e):
         B, T = c.x.shape
         c.dx = KM.msd_input_dgrad(c.dpre, c.ops[e["layer"]].w32).view(B, 1, T)
-
-    _HANDLERS = dict(_Discriminator._HANDLERS, sn_power=_do_sn_power, sn_scale=_do_sn_scale, fold=_do_fold, input=_do_input, gconv=_do_gconv,
-                     gconv_wgrad=_do_gconv_wgrad, input_wgrad=_do_input_wgrad, sn_finish=_do_sn_finish, gfold_bwd=_do_gfold_bwd,
-                     gconv_dgrad=_do_gconv_dgrad, input_dgrad=_do_input_dgrad)
 
 
 class MultiScaleDiscriminator(nn.Module):
@@ -531,6 +502,18 @@ class MultiScaleDiscriminator(nn.Module):
         for i, d in enumerate(self.discriminators):
             plan += [dict(e, scale=i) for e in d.backward_plan(need_dx, need_params)]
         return plan + ([dict(kind="pool_bwd", scale=2), dict(kind="pool_bwd", scale=1)] if need_dx else [])
+
+    def calls(self, stage, backward=None):
+        """As MultiPeriodDiscriminator.calls; in a backward the adjoint of a pool runs after the scale it feeds."""
+        fwd, bwd = _PoolFunction.CALLS
+        out = []
+        for i, d in enumerate(self.discriminators):
+            if backward is None:
+                out += ([dict(kind="pool", scale=i, stage=stage, call=fwd)] if i else []) + d.calls([dict(e, scale=i) for e in d.launch_plan()], stage)
+            else:
+                pool = [dict(kind="pool_bwd", scale=i, stage=stage, call=bwd)] if backward[0] and i else []
+                out = d.calls([dict(e, scale=i) for e in d.backward_plan(*backward)], stage) + pool + out
+        return out
 
     def forward(self, x):
         scores, feats = [], []
@@ -558,6 +541,11 @@ class HifiganDiscriminator(nn.Module):
 
     def backward_plan(self, need_dx=False, need_params=True):
         return self.mpd.backward_plan(need_dx, need_params) + self.msd.backward_plan(need_dx, need_params)
+
+    def calls(self, stage, backward=None):
+        """As the halves' `calls`: mpd then msd in a forward, the reverse in a backward."""
+        halves = (self.mpd, self.msd) if backward is None else (self.msd, self.mpd)
+        return [c for h in halves for c in h.calls(stage, backward)]
 
     def forward(self, x):
         scores, feats = self.mpd(x)

@@ -8,8 +8,11 @@ prologues and epilogues, so a call of the default configuration is 79 launches (
 
 Fine-tuning (reference: urhythmic_fine_tune_vocoder.py:191-222): `generator.trainable()` makes forward() return a tensor with a
 grad_fn; one autograd Function takes every parameter as an input, so `.grad`, accumulation, zero_grad and DDP hooks work as on any
-module.  The input never gets a gradient (units / mels are data).  One backward pass is `backward_plan()`."""
-import math
+module.  The input never gets a gradient (units / mels are data).  One training forward is `train_plan()` (the folds, the
+convolutions and, in bf16 mode, the casts of the stored activations), one backward pass `backward_plan()`.
+
+The three lists are walked through one table from `kind` to handler (vocoder/plan.py) and built once per module."""
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -17,10 +20,12 @@ from torch import nn
 
 from ..ops import functional as Fn
 from ..ops import kernels_vocoder as KV
+from .plan import Layer, PlanExecutor, WNConv, fold_calls, handles
 
 LRELU_SLOPE = 0.1
 POST_SLOPE = 0.01        # vocoder.py:103 applies F.leaky_relu with torch's DEFAULT slope in front of conv_post
 KINDS = ("input", "conv1d", "tconv1d", "conv_out")   # the input launch + the kernel families a call may launch ("fold" runs at load)
+TRAIN_KINDS = ("fold", "fold_bwd") + KINDS + ("cast",)     # a training forward folds from the live parameters and keeps its buffers
 BWD_KINDS = ("conv_out_bwd", "wgrad", "finish", "conv1d_dgrad", "tconv1d_dgrad")    # the launches of one backward pass
 
 
@@ -69,43 +74,10 @@ def stage_lengths(lens, factors):
     return out
 
 
-# ---------------------------------------------------------------------------------------------------------------------------
-# parameters
-# ---------------------------------------------------------------------------------------------------------------------------
-class _WNConv(nn.Module):
-    """Parameters of one weight-normed convolution in either checkpoint form: (bias, weight_g, weight_v) or (bias, weight)."""
-
-    def __init__(self, wshape, nbias, fan_in):
-        super().__init__()
-        self.wshape = tuple(wshape)
-        bound = 1.0 / math.sqrt(fan_in)
-        v = torch.empty(*wshape).uniform_(-bound, bound)
-        self.bias = nn.Parameter(torch.empty(nbias).uniform_(-bound, bound))
-        self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
-        self.weight_v = nn.Parameter(v)
-
-    @property
-    def normed(self):
-        return "weight_v" in self._parameters
-
-    def set_form(self, normed, weight=None):
-        if normed == self.normed and weight is None:
-            return
-        ref = self.bias
-        for name in ("weight_g", "weight_v", "weight"):
-            self._parameters.pop(name, None)
-        if normed:
-            v = torch.zeros(self.wshape, dtype=ref.dtype, device=ref.device) if weight is None else weight
-            self.weight_g = nn.Parameter(v.flatten(1).norm(dim=1).view(-1, 1, 1))
-            self.weight_v = nn.Parameter(v)
-        else:
-            self.weight = nn.Parameter(torch.zeros(self.wshape, dtype=ref.dtype, device=ref.device) if weight is None else weight)
-
-
 class ResBlock(nn.Module):
     def __init__(self, channels, kernel_size=3, dilation=(1, 3, 5)):
         super().__init__()
-        mk = lambda: _WNConv((channels, channels, kernel_size), channels, channels * kernel_size)   # noqa: E731
+        mk = lambda: WNConv((channels, channels, kernel_size))   # noqa: E731
         self.convs1 = nn.ModuleList([mk() for _ in dilation])
         self.convs2 = nn.ModuleList([mk() for _ in dilation])
 
@@ -115,8 +87,9 @@ class _GeneratorFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, gen, x, taps, *params):
-        y, state = gen._forward_train(x, taps)
-        ctx.gen, ctx.state = gen, state
+        B, _, N = x.shape
+        ctx.gen, ctx.state = gen, gen._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), train=True, taps=taps)
+        y = ctx.state.y.view(B, 1, -1)
         ctx.save_for_backward(y, *params)       # the parameters: autograd refuses a backward after an in-place update of one
         return y
 
@@ -127,7 +100,7 @@ class _GeneratorFunction(torch.autograd.Function):
         return (None, None, None) + tuple(ctx.gen._backward(ctx.state, y, dy))
 
 
-class HifiganGenerator(nn.Module):
+class HifiganGenerator(PlanExecutor):
     """HiFi-GAN generator (reference urhythmic/vocoder.py:23-114).  x (B, in_channels, N) -> (B, 1, N * prod(factors)).  Inference
     only until `trainable()` is called; then forward() under grad mode carries the parameter gradients."""
 
@@ -148,18 +121,18 @@ class HifiganGenerator(nn.Module):
         self.resblock_kernel_sizes = tuple(resblock_kernel_sizes)
         self.resblock_dilation_sizes = tuple(tuple(d) for d in resblock_dilation_sizes)
         self.num_kernels, self.num_upsamples = len(resblock_kernel_sizes), len(upsample_factors)
-        self.conv_pre = _WNConv((upsample_channels, in_channels, 5), upsample_channels, in_channels * 5)
+        self.conv_pre = WNConv((upsample_channels, in_channels, 5))
         self.ups = nn.ModuleList()
         self.resblocks = nn.ModuleList()
         for i, (u, k) in enumerate(zip(upsample_factors, upsample_kernel_sizes)):
             cin, cout = upsample_channels // 2 ** i, upsample_channels // 2 ** (i + 1)
-            self.ups.append(_WNConv((cin, cout, k), cout, cout * k))
+            self.ups.append(WNConv((cin, cout, k), cout))
         for i in range(self.num_upsamples):
             ch = upsample_channels // 2 ** (i + 1)
             for k, d in zip(resblock_kernel_sizes, resblock_dilation_sizes):
                 self.resblocks.append(ResBlock(ch, k, d))
-        self.conv_post = _WNConv((1, ch, 7), 1, ch * 7)
-        self._ops = {}            # compute dtype -> {layer name: (operand, bias fp32)}
+        self.conv_post = WNConv((1, ch, 7))
+        self._ops = {}            # compute dtype -> {layer name: Layer(operand, bias fp32)}: the inference path's cache
         self._trainable = False
 
     def trainable(self, mode=True):
@@ -167,14 +140,14 @@ class HifiganGenerator(nn.Module):
         returns a tensor with a grad_fn whose backward fills the .grad of every parameter, and EVERY call -- under no_grad and
         the batched ones too -- folds its operands from the live parameters, so an optimiser's in-place update is seen by the
         next call.  An input that requires grad is refused in either mode.  Under Fn.set_compute_dtype(bfloat16) the backward runs in
-        bf16 (fp32 accumulation, fp32 parameter gradients) while the training forward keeps fp32 activations (_forward_train)."""
+        bf16 (fp32 accumulation, fp32 parameter gradients) while the training forward keeps fp32 activations (train_plan)."""
         self._trainable = bool(mode)
         self._drop_cache()
         return self
 
     # ---- checkpoint forms -------------------------------------------------------------------------------------------------
     def _leaves(self):
-        return [(n, m) for n, m in self.named_modules() if isinstance(m, _WNConv)]
+        return [(n, m) for n, m in self.named_modules() if isinstance(m, WNConv)]
 
     def _drop_cache(self):
         self._ops = {}
@@ -212,27 +185,17 @@ class HifiganGenerator(nn.Module):
             return 1, self.upsample_factors[int(name.split(".")[1])]
         return (2, 1) if name == "conv_post" else (0, 1)
 
-    @staticmethod
-    def _vg(m):
-        """(v, g) fp32 contiguous of a layer in either checkpoint form; g is None without weight norm"""
-        if m.normed:
-            return m.weight_v.detach().float().contiguous(), m.weight_g.detach().float().contiguous()
-        return m.weight.detach().float().contiguous(), None
-
     def _fold(self, name, m, dtype, want_w32=True, want_op=True):
         mode, u = self._layer_mode(name)
         with torch.no_grad():
-            v, g = self._vg(m)
+            v, g = m.vg()
             return KV.hifigan_fold(mode, v, g, torch.float32 if dtype is None else dtype, u=u, want_w32=want_w32, want_op=want_op)
 
     def _operands(self, dtype):
         """Folded weights in the kernels' layouts for `dtype`: built once per load / device move, on the device."""
         if dtype not in self._ops:
-            ops = {}
-            for name, m in self._leaves():
-                _, op = self._fold(name, m, dtype, want_w32=False)
-                ops[name] = (op, m.bias.detach().float().contiguous())
-            self._ops[dtype] = ops
+            self._ops[dtype] = {name: Layer(None, None, m.bias.detach().float().contiguous(), op=self._fold(name, m, dtype, want_w32=False)[1])
+                                for name, m in self._leaves()}
         return self._ops[dtype]
 
     # ---- the launch list --------------------------------------------------------------------------------------------------
@@ -270,10 +233,22 @@ class HifiganGenerator(nn.Module):
         plan.append(dict(kind="conv_out", layer="conv_post", src=cur, k=7, cin=ch, slope=POST_SLOPE, mul=mul))
         return plan
 
-    def _train_plan(self):
-        """launch_plan() with every convolution's output in a buffer of its own (the backward reads them all): the ping-pong
-        buffers t{i} / a{i} / b{i} become `<layer>.out`."""
-        plan, cur = [], {}
+    def train_plan(self, dtype=None):
+        """What one training forward launches, in order: dicts with `kind` in TRAIN_KINDS.  Per leaf the fold from the live parameters
+        (`op`: it lays out the operand too) and, for every layer whose input gets a gradient, the data gradient's operand; then
+        launch_plan() with every convolution's output in a buffer of its own (the backward reads them all): the ping-pong buffers
+        t{i} / a{i} / b{i} become `<layer>.out`; then, in bf16 mode (dtype: the compute dtype, None = the current one), one cast
+        launch per kept buffer.  _run(train=True) executes exactly this list.
+        The training forward keeps fp32 activations in EITHER compute mode: a leaky-relu mask is the sign of a stored
+        pre-activation, and a bf16 forward's error flips hundreds of them (370 of 170 880 on the tests' tiny model, which alone
+        puts every gradient 5 - 20 % from the exact one).  In bf16 mode the backward's GEMMs run in bf16 over copies of the stored
+        tensors that one cast launch each (the input kernel) rounds to bf16 -- a rounding keeps the sign, so no mask flips."""
+        plan, cur, kept = [], {}, []
+        for name, _ in self._leaves():
+            mode, u = self._layer_mode(name)
+            plan.append(dict(kind="fold", layer=name, mode=mode, u=u, op=True))
+            if mode != 2 and name != "conv_pre":
+                plan.append(dict(kind="fold_bwd", layer=name, mode=mode, u=u))
         for e in self.launch_plan():
             e = dict(e)
             for key in ("src", "res"):
@@ -282,21 +257,25 @@ class HifiganGenerator(nn.Module):
             dst = e.get("dst")
             if dst is not None and dst[0] in "tab" and dst[1:].isdigit():
                 cur[dst] = e["dst"] = e["layer"] + ".out"
+            if dst is not None and e["dst"] not in kept:
+                kept.append(e["dst"])
             plan.append(e)
+        if (Fn.compute_dtype() if dtype is None else dtype) != torch.float32:
+            plan += [dict(kind="cast", src=name) for name in kept]
         return plan
 
     def backward_plan(self):
         """What one backward pass launches, in order: dicts with `kind` in BWD_KINDS.  `d:<buffer>` names the gradient of a forward
-        buffer of _train_plan().  Per convolution: the weight / bias partials ("wgrad"; conv_post's come from "conv_out_bwd"), the
+        buffer of train_plan().  Per convolution: the weight / bias partials ("wgrad"; conv_post's come from "conv_out_bwd"), the
         "finish" launch that writes the parameters' gradients, and -- except for conv_pre, whose input is data -- the data gradient.
         Every gradient buffer is written by one launch; d:up{i} is accumulated by the first unit of every ResBlock of the stage.
         The residual x' = conv2(..) + x is the `res` of conv1's data gradient, and the 1 / num_kernels of the MRF average is the
         `scale` of the launch that produces d:s{i}.  _backward() executes exactly this list."""
         nk = self.num_kernels
         plan, pending, written = [], {}, set()
-        for e in reversed(self._train_plan()):
+        for e in reversed(self.train_plan(torch.float32)):
             kind, layer = e["kind"], e.get("layer")
-            if kind == "input":
+            if kind not in KINDS[1:]:
                 continue
             if kind == "conv_out":
                 plan.append(dict(kind="conv_out_bwd", layer=layer, src=e["src"], dst="d:" + e["src"], k=e["k"], cin=e["cin"], slope=e["slope"],
@@ -324,65 +303,6 @@ class HifiganGenerator(nn.Module):
             plan.append(d)
         return plan
 
-    # ---- training ---------------------------------------------------------------------------------------------------------
-    def _forward_train(self, x, taps):
-        """The training forward keeps fp32 activations in EITHER compute mode: a leaky-relu mask is the sign of a stored
-        pre-activation, and a bf16 forward's error flips hundreds of them (370 of 170 880 on the tests' tiny model, which alone
-        puts every gradient 5 - 20 % from the exact one).  In bf16 mode the backward's GEMMs run in bf16 over copies of the stored
-        tensors that one cast launch each (the input kernel) rounds to bf16 -- a rounding keeps the sign, so no mask flips."""
-        dtype = Fn.compute_dtype()
-        ops, state = {}, {}
-        for name, m in self._leaves():
-            mode, u = self._layer_mode(name)
-            v, g = self._vg(m)
-            w32, op = KV.hifigan_fold(mode, v, g, torch.float32, u=u)
-            opT = KV.hifigan_fold_bwd(mode, w32, dtype, u=u) if mode != 2 and name != "conv_pre" else None
-            ops[name] = (op, m.bias.detach().float().contiguous())
-            state[name] = (v, g, op, opT)
-        bufs = {}
-        B, _, N = x.shape
-        y = self._run(x.detach(), B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps, plan=self._train_plan(), ops=ops, keep=bufs,
-                      dtype=torch.float32)
-        if dtype != torch.float32:
-            bufs = {k: KV.hifigan_input(v, v.shape[0], v.shape[1], v.shape[2], (v.stride(0), v.stride(1), v.stride(2)), dtype)
-                    for k, v in bufs.items()}
-        state[":bufs"], state[":dtype"] = bufs, dtype
-        return y.view(B, 1, -1), state
-
-    def _backward(self, state, y, dy):
-        """Gradients of every parameter, in named_parameters() order, from dy (B, 1, L): executes backward_plan()."""
-        bufs, dtype = state[":bufs"], state[":dtype"]
-        B, L = y.shape[0], y.shape[-1]
-        y2, dy2 = y.detach().reshape(B, L).contiguous(), dy.detach().float().reshape(B, L).contiguous()
-        grads, parts, out = {}, None, {}
-        with torch.no_grad():
-            for e in self.backward_plan():
-                kind, layer = e["kind"], e["layer"]
-                v, g, op, opT = state[layer]
-                if kind == "conv_out_bwd":
-                    grads[e["dst"]], wp, bp = KV.hifigan_conv_out_bwd(bufs[e["src"]], op, y2, dy2, e["k"], slope=e["slope"], scale=e["scale"])
-                    parts = (wp, bp)
-                elif kind == "wgrad":
-                    parts = KV.hifigan_wgrad(e["conv"], grads[e["dy"]], bufs[e["src"]], e["k"], e["step"], slope=e["slope"])
-                elif kind == "finish":
-                    out[layer] = KV.hifigan_wgrad_finish(e["mode"], parts[0], parts[1], v, g, u=e["u"])
-                    parts = None
-                elif kind == "tconv1d_dgrad":
-                    grads[e["dst"]] = KV.hifigan_tconv1d_dgrad(grads[e["dy"]], opT, e["k"], e["u"], e["cin"], mask_src=bufs[e["mask"]],
-                                                               slope=e["slope"], scale=e["scale"])
-                else:
-                    res = grads[e["res"]] if e.get("res") else None
-                    grads[e["dst"]] = KV.hifigan_conv1d_dgrad(grads[e["dy"]], opT, e["k"], e["dil"], e["cin"], mask_src=bufs[e["mask"]],
-                                                              slope=e["slope"], res=res, accumulate=e["accumulate"], scale=e["scale"],
-                                                              out=grads.get(e["dst"]))
-        result = []
-        for name, p in self.named_parameters():
-            layer, leaf = name.rsplit(".", 1)
-            gw, gg, gb = out[layer]
-            t = gb if leaf == "bias" else (gg if leaf == "weight_g" else gw)
-            result.append(t.view_as(p).to(p.dtype))
-        return result
-
     # ---- execution --------------------------------------------------------------------------------------------------------
     @staticmethod
     def _check_input(x, grad_refusal):
@@ -393,38 +313,99 @@ class HifiganGenerator(nn.Module):
         if x.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("HifiganGenerator input: float32 or bfloat16")
 
-    def _run(self, x, B, N, strides, vlens=None, a=None, b=None, taps=None, plan=None, ops=None, keep=None, dtype=None):
-        self._check_input(x, "HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
-        dtype = Fn.compute_dtype() if dtype is None else dtype
-        if ops is None:
+    def _run(self, x, B, N, strides, train=False, **fields):
+        """One forward call -> its state, `c` of the handlers: the input with its (batch, frame, channel) strides, ops: layer -> Layer,
+        dtype of the activations, bufs: name -> activation, y = the waveform, and in `fields` what forward_batch (vlens, a, b) and the
+        tests (taps) pass.  train: walk train_plan() -- the operands are folded from the live parameters, the activations are fp32 in
+        either compute mode, bwd_dtype is the backward's, and w32 is the folded weight a fold hands the launch after it."""
+        dtype = Fn.compute_dtype()
+        if not train:
+            self._check_input(x, "HifiganGenerator is inference only: no backward pass (call it under torch.no_grad() or detach the input)")
             if self._trainable:                  # an optimiser updates the parameters in place: fold from the live values
                 self._drop_cache()
-            ops = self._operands(dtype)
-        bufs, y = ({} if keep is None else keep), None
-        with torch.no_grad():
-            for e in (self.launch_plan() if plan is None else plan):
-                kind = e["kind"]
-                if kind == "input":
-                    bufs[e["dst"]] = KV.hifigan_input(x.detach(), B, N, e["cout"], strides, dtype, a=a, b=b, vlens=vlens)
-                    continue
-                w, bias = ops[e["layer"]]
-                src = bufs[e["src"]]
-                if kind == "conv_out":
-                    y, pre = KV.hifigan_conv_out(src, w, bias, e["k"], slope=e["slope"], tanh=True, want_pre=taps is not None, vlens=vlens,
-                                                 vmul=e["mul"])
-                    if taps is not None:
-                        taps["conv_post"] = pre
-                elif kind == "tconv1d":
-                    bufs[e["dst"]] = KV.hifigan_tconv1d(src, w, bias, e["k"], e["u"], e["cout"], slope=e["slope"], out=bufs.get(e["dst"]),
-                                                        vlens=vlens, vmul=e["mul"])
-                else:
-                    res = bufs[e["res"]] if "res" in e else None
-                    bufs[e["dst"]] = KV.hifigan_conv1d(src, w, bias, e["k"], e["dil"], e["cout"], slope=e["slope"], res=res,
-                                                       accumulate=e.get("accumulate", False), scale=e.get("scale", 1.0),
-                                                       out=bufs.get(e["dst"]), vlens=vlens, vmul=e["mul"])
-                if taps is not None and "tap" in e:
-                    taps[e["tap"]] = bufs[e["dst"]]
-        return y
+        c = SimpleNamespace(x=x.detach(), B=B, N=N, strides=strides, ops={} if train else self._operands(dtype), bufs={}, y=None, w32=None,
+                            dtype=torch.float32 if train else dtype, bwd_dtype=dtype, vlens=None, a=None, b=None, taps=None)
+        c.__dict__.update(fields, leaves=dict(self._leaves()) if train else None)
+        self._walk(self._plan("train_plan", dtype) if train else self._plan("launch_plan"), c)
+        return c
+
+    def _backward(self, state, y, dy):
+        """Gradients of every parameter, in named_parameters() order, from dy (B, 1, L): executes backward_plan().  The state of the
+        pass: the forward's ops and bufs, y and dy as (B, L), grads: `d:<buffer>` -> gradient, parts = the partials one launch hands
+        the finish launch, out: layer -> (grad_weight, grad_g, grad_bias)."""
+        B, L = y.shape[0], y.shape[-1]
+        c = SimpleNamespace(ops=state.ops, bufs=state.bufs, y=y.detach().reshape(B, L).contiguous(),
+                            dy=dy.detach().float().reshape(B, L).contiguous(), grads={}, parts=None, out={})
+        self._walk(self._plan("backward_plan"), c)
+        return self._param_grads(c.out)
+
+    # ---- the handlers: `calls` names the library calls each makes ---------------------------------------------------------------
+    @handles("fold", fold_calls)
+    def _do_fold(self, c, e):
+        leaf = c.leaves[e["layer"]]
+        v, g = leaf.vg()
+        c.w32, op = KV.hifigan_fold(e["mode"], v, g, torch.float32, u=e["u"], want_op=e["op"])
+        c.ops[e["layer"]] = Layer(v, g, leaf.bias.detach().float().contiguous(), op=op)
+
+    @handles("fold_bwd", "fill_zero", "hifigan_fold_bwd")
+    def _do_fold_bwd(self, c, e):
+        c.ops[e["layer"]].opT = KV.hifigan_fold_bwd(e["mode"], c.w32, c.bwd_dtype, u=e["u"])
+
+    @handles("input", "hifigan_input")
+    def _do_input(self, c, e):
+        c.bufs[e["dst"]] = KV.hifigan_input(c.x, c.B, c.N, e["cout"], c.strides, c.dtype, a=c.a, b=c.b, vlens=c.vlens)
+
+    @handles("cast", "hifigan_input")
+    def _do_cast(self, c, e):
+        v = c.bufs[e["src"]]
+        c.bufs[e["src"]] = KV.hifigan_input(v, v.shape[0], v.shape[1], v.shape[2], (v.stride(0), v.stride(1), v.stride(2)), c.bwd_dtype)
+
+    def _store(self, c, e, t):
+        c.bufs[e["dst"]] = t
+        if c.taps is not None and "tap" in e:
+            c.taps[e["tap"]] = t
+
+    @handles("conv1d", "hifigan_conv1d")
+    def _do_conv1d(self, c, e):
+        o = c.ops[e["layer"]]
+        self._store(c, e, KV.hifigan_conv1d(c.bufs[e["src"]], o.op, o.bias, e["k"], e["dil"], e["cout"], slope=e["slope"],
+                                            res=c.bufs[e["res"]] if "res" in e else None, accumulate=e.get("accumulate", False),
+                                            scale=e.get("scale", 1.0), out=c.bufs.get(e["dst"]), vlens=c.vlens, vmul=e["mul"]))
+
+    @handles("tconv1d", "hifigan_tconv1d")
+    def _do_tconv1d(self, c, e):
+        o = c.ops[e["layer"]]
+        self._store(c, e, KV.hifigan_tconv1d(c.bufs[e["src"]], o.op, o.bias, e["k"], e["u"], e["cout"], slope=e["slope"],
+                                             out=c.bufs.get(e["dst"]), vlens=c.vlens, vmul=e["mul"]))
+
+    @handles("conv_out", "hifigan_conv_out")
+    def _do_conv_out(self, c, e):
+        o = c.ops[e["layer"]]
+        c.y, pre = KV.hifigan_conv_out(c.bufs[e["src"]], o.op, o.bias, e["k"], slope=e["slope"], tanh=True, want_pre=c.taps is not None,
+                                       vlens=c.vlens, vmul=e["mul"])
+        if c.taps is not None:
+            c.taps["conv_post"] = pre
+
+    @handles("conv_out_bwd", "hifigan_conv_out_bwd")
+    def _do_conv_out_bwd(self, c, e):
+        c.grads[e["dst"]], wp, bp = KV.hifigan_conv_out_bwd(c.bufs[e["src"]], c.ops[e["layer"]].op, c.y, c.dy, e["k"], slope=e["slope"],
+                                                            scale=e["scale"])
+        c.parts = (wp, bp)
+
+    @handles("wgrad", "hifigan_wgrad")
+    def _do_wgrad(self, c, e):
+        c.parts = KV.hifigan_wgrad(e["conv"], c.grads[e["dy"]], c.bufs[e["src"]], e["k"], e["step"], slope=e["slope"])
+
+    @handles("tconv1d_dgrad", "hifigan_tconv1d_dgrad")
+    def _do_tconv1d_dgrad(self, c, e):
+        c.grads[e["dst"]] = KV.hifigan_tconv1d_dgrad(c.grads[e["dy"]], c.ops[e["layer"]].opT, e["k"], e["u"], e["cin"],
+                                                     mask_src=c.bufs[e["mask"]], slope=e["slope"], scale=e["scale"])
+
+    @handles("conv1d_dgrad", "hifigan_conv1d_dgrad")
+    def _do_conv1d_dgrad(self, c, e):
+        c.grads[e["dst"]] = KV.hifigan_conv1d_dgrad(c.grads[e["dy"]], c.ops[e["layer"]].opT, e["k"], e["dil"], e["cin"],
+                                                    mask_src=c.bufs[e["mask"]], slope=e["slope"], res=c.grads[e["res"]] if e.get("res") else None,
+                                                    accumulate=e["accumulate"], scale=e["scale"], out=c.grads.get(e["dst"]))
 
     def forward(self, x, taps=None):
         """x (B, in_channels, N) -> (B, 1, N * prod(upsample_factors)) fp32.  taps: a dict that receives the channel-last outputs of
@@ -435,8 +416,7 @@ class HifiganGenerator(nn.Module):
         if self._trainable and torch.is_grad_enabled():
             self._check_input(x, "HifiganGenerator computes no input gradient: the units / mel are data (detach the input)")
             return _GeneratorFunction.apply(self, x, taps, *[p for _, p in self.named_parameters()])
-        y = self._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps)
-        return y.view(B, 1, -1)
+        return self._run(x, B, N, (x.stride(0), x.stride(2), x.stride(1)), taps=taps).y.view(B, 1, -1)
 
     def forward_batch(self, xs, lens, a=None, b=None, host_lens=None):
         """xs (B, Nmax, in_channels) channel-last, zero-padded (whatever the padding holds is never read); lens (B) mel frames ->
@@ -457,7 +437,7 @@ class HifiganGenerator(nn.Module):
             if len(host) != B or any(n < 0 or n > N for n in host):
                 raise ValueError("forward_batch: one length per row, 0 <= lens[b] <= Nmax")
         vlens = lens if on_device else torch.tensor(host, dtype=torch.int32).to(xs.device)
-        y = self._run(xs, B, N, (xs.stride(0), xs.stride(1), xs.stride(2)), vlens=vlens, a=a, b=b)
+        y = self._run(xs, B, N, (xs.stride(0), xs.stride(1), xs.stride(2)), vlens=vlens, a=a, b=b).y
         if host is None:
             host = [min(max(int(n), 0), N) for n in lens.tolist()]
         total = stage_lengths(host, self.upsample_factors)[-1]

@@ -14,6 +14,7 @@ import torch.nn.functional as F
 
 import vocoder_bwd_ref as VB
 import vocoder_ref as VR
+from seq2seq_vc_amd import _lib
 from seq2seq_vc_amd.ops import functional as Fn
 from seq2seq_vc_amd.ops import kernels_vocoder as KV
 from seq2seq_vc_amd.vocoder import HifiganGenerator
@@ -427,5 +428,41 @@ def two_sgd_steps():
     return res
 
 
+def _recorded(fn):
+    """the names of the library calls fn() makes, in order"""
+    real, names = _lib.check, []
+
+    def counting(rc, what):
+        names.append(what)
+        return real(rc, what)
+    _lib.check = counting
+    try:
+        fn()
+    finally:
+        _lib.check = real
+    return names
+
+
+def plans_are_the_recorded_calls():
+    """The library calls of one trainable forward (tiny generator, B = 2, 8 frames) are calls(train_plan(dtype)) and those of its
+    backward calls(backward_plan()), name for name and in order; bf16 mode adds the casts of the kept buffers to the forward."""
+    res = []
+    gen = HifiganGenerator(**VR.TINY_CFG).to(DEV).trainable()
+    x = torch.randn(2, VR.TINY_CFG["in_channels"], 8, generator=torch.Generator().manual_seed(16)).to(DEV)
+    for dtype in (torch.float32, torch.bfloat16):
+        tag = "fp32" if dtype == torch.float32 else "bf16"
+        with _mode(dtype):
+            y = []
+            fwd = _recorded(lambda: y.append(gen(x)))
+            bwd = _recorded(lambda: y[0].sum().backward())
+        want_fwd = [e["call"] for e in gen.calls(gen.train_plan(dtype))]
+        want_bwd = [e["call"] for e in gen.calls(gen.backward_plan())]
+        casts = sum(1 for e in gen.train_plan(dtype) if e["kind"] == "cast")
+        res.append((fwd == want_fwd and (casts > 0) == (dtype != torch.float32),
+                    f"{tag}: {len(fwd)} recorded calls of the training forward, {len(want_fwd)} in calls(train_plan()) ({casts} casts), equal in order: {fwd == want_fwd}"))
+        res.append((bwd == want_bwd, f"{tag}: {len(bwd)} recorded calls of the backward, {len(want_bwd)} in calls(backward_plan()), equal in order: {bwd == want_bwd}"))
+    return res
+
+
 CASES = [dgrad_conv1d_kernel, dgrad_tconv1d_kernel, wgrad_kernels, conv_out_bwd_kernel, finish_weight_norm_kernel, model_gradients_fp32,
-         model_gradients_bf16, two_sgd_steps]
+         model_gradients_bf16, two_sgd_steps, plans_are_the_recorded_calls]

@@ -185,6 +185,35 @@ def test_fine_tuner_checkpoint_layout_and_plan():
     assert len(D.backward_plan(True, False)) < len(D.backward_plan(True, True))
 
 
+def test_every_plan_kind_has_a_handler_that_names_known_library_calls():
+    import itertools
+    import os
+    import re
+
+    from seq2seq_vc_amd.urhythmic import vocoder as V
+    gen = HifiganGenerator(**VR.TINY_CFG)
+    cases = [(gen, gen.launch_plan() + gen.train_plan(torch.float32) + gen.train_plan(torch.bfloat16) + gen.backward_plan())]
+    for net in (V.PeriodDiscriminator(3), V.ScaleDiscriminator(), V.ScaleDiscriminator(use_spectral_norm=True)):
+        for training in (True, False):
+            net.train(training)
+            cases.append((net, net.launch_plan() + [e for flags in itertools.product((False, True), repeat=2) for e in net.backward_plan(*flags)]))
+    for net, plan in cases:
+        expanded = []
+        for e in plan:
+            handler = net._HANDLERS[e["kind"]]
+            names = handler.calls(e) if callable(handler.calls) else handler.calls
+            assert names and all("s2svc_" + n in _lib._FUNCTIONS for n in names), (type(net).__name__, e["kind"], names)
+            expanded += [dict(e, stage="s", call=n) for n in names]
+        assert net.calls(plan, "s") == expanded
+    assert all("s2svc_" + n in _lib._FUNCTIONS for n in V._PoolFunction.CALLS)
+    assert all("s2svc_" + e["call"] in _lib._FUNCTIONS for e in _tuner("reference").launch_plan())
+    # the handler registrations are the only place that maps a kind to library calls
+    pkg = os.path.dirname(_lib.__file__)
+    for path in ("urhythmic/fine_tune.py", "urhythmic/vocoder.py", "vocoder/hifigan.py", "vocoder/plan.py"):
+        src = open(os.path.join(pkg, path)).read()
+        assert "_CALLS" not in src and not re.search(r'"\w+":\s*\(?\s*"(hifigan_|fill_zero)', src), path
+
+
 def test_refusals_on_the_host():
     with pytest.raises(TypeError):
         VocoderFineTuner(torch.nn.Linear(2, 2), HifiganDiscriminator())

@@ -162,9 +162,20 @@ def test_backward_plan_of_the_default_configuration():
     c1 = [e for e in plan if e["kind"] == "conv1d_dgrad" and ".convs1." in e["layer"]]
     assert len(c1) == 36 and all(e["res"] is not None and e["mask"] == e["dst"][2:] for e in c1)
     # the training forward keeps every convolution's input: no buffer is written twice except the stage sums
-    fwd = gen._train_plan()
+    train = gen.train_plan(torch.float32)
+    fwd = [e for e in train if e["kind"] in H.KINDS]
     dsts = [e["dst"] for e in fwd if "dst" in e and not e.get("accumulate")]
     assert len(dsts) == len(set(dsts)) and [e["kind"] for e in fwd] == [e["kind"] for e in gen.launch_plan()]
+    # in front of the convolutions: one fold per leaf, and the data gradient's operand for every leaf but conv_pre and conv_post
+    leaves = [name for name, _ in gen._leaves()]
+    folds = train[:-len(fwd)]
+    assert train[len(folds):] == fwd and {e["kind"] for e in folds} == {"fold", "fold_bwd"} and set(H.TRAIN_KINDS) >= {e["kind"] for e in train}
+    assert [e["layer"] for e in folds if e["kind"] == "fold"] == leaves and all(e["op"] for e in folds if e["kind"] == "fold")
+    assert [e["layer"] for e in folds if e["kind"] == "fold_bwd"] == [name for name in leaves if name not in ("conv_pre", "conv_post")]
+    # bf16 mode: the same list, then one cast per kept buffer
+    bf16 = gen.train_plan(torch.bfloat16)
+    assert bf16[:len(train)] == train and [e["kind"] for e in bf16[len(train):]] == ["cast"] * len(set(dsts))
+    assert sorted(e["src"] for e in bf16[len(train):]) == sorted(set(dsts))
 
 
 def test_trainable_off_changes_nothing_on_the_host():

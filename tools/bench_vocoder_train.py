@@ -150,7 +150,7 @@ def main():
     nleaves = len(gen._leaves())
     res = {"metric": "HiFi-GAN generator forward + backward (parameter gradients), default configuration",
            "launches": {"forward": len(fwd), "fold (per step, from the live parameters)": 2 * nleaves - 2, "backward": len(bwd),
-                        "casts of the stored fp32 activations (bf16 mode only)": len({e["dst"] for e in gen._train_plan() if "dst" in e})},
+                        "casts of the stored fp32 activations (bf16 mode only)": sum(1 for e in gen.train_plan(torch.bfloat16) if e["kind"] == "cast")},
            "repeats": a.repeats, "timed": "device events around back-to-back steps; median [min, max] over the repeats, HIP and stock-torch "
            "groups alternated", "shapes": {}}
     if torch_err:
