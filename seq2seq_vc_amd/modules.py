@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from .ops import functional as Fn
+from .ops import functional_attn as FAttn
 from .ops import kernels as K
 
 # ------------------------------------------------------------------------------------------------
@@ -358,43 +359,38 @@ class MultiHeadedAttention(nn.Module):
         residual from the alias, whose gradient then rides in the query projection's data-gradient GEMM (Fn.linear)."""
         kl = None if klens is None else klens.dev
         f = getattr(self, "_fused", None)   # packed Q/K/V views of the flat parameter buffer (optim.FlatAdam)
-        qp = None
         wo, bo = self.linear_out.weight, self.linear_out.bias
+        p = self._p()
         packed = f is not None and key is value and (query is not key or "w_qkv" in f)
-        if (kv is not None or packed) and Fn.attn_block_ok(query, (key if kv is None else kv).shape[1], kv, self.h, wo):
-            # short sequences, bf16, training: projection + core + out-projection as one autograd node (its backward folds the
-            # out-projection's data gradient into the core's launch)
-            if kv is None and query is key:
-                r = Fn.attention_block_qkv(query, f["w_qkv"], f["b_qkv"], wo, bo, kl, causal, self.h, self._p(), passthrough)
-            else:
-                if kv is None:
-                    kv = Fn.linear(key, f["w_kv"], f["b_kv"])                           # ONE GEMM, N = 2D
-                r = Fn.attention_block_kv(query, f["w_q"], f["b_q"], kv, wo, bo, kl, causal, self.h, self._p(), passthrough)
-            self.attn = r[1]
-            return (r[0], r[2]) if passthrough else r[0]
-        if kv is not None:
-            q = Fn.linear(query, f["w_q"], f["b_q"], passthrough=passthrough)
-            if passthrough:
-                q, qp = q
-            ctx, self.attn = Fn.attention_packed_kv(q, kv, kl, causal, self.h, self._p())
-        elif packed:
-            if query is key:
-                qkv = Fn.linear(query, f["w_qkv"], f["b_qkv"], passthrough=passthrough)   # ONE GEMM, N = 3D
-                if passthrough:
-                    qkv, qp = qkv
-                ctx, self.attn = Fn.attention_packed_qkv(qkv, kl, causal, self.h, self._p())
-            else:
-                q = Fn.linear(query, f["w_q"], f["b_q"], passthrough=passthrough)
-                if passthrough:
-                    q, qp = q
-                kv = Fn.linear(key, f["w_kv"], f["b_kv"])                           # ONE GEMM, N = 2D
-                ctx, self.attn = Fn.attention_packed_kv(q, kv, kl, causal, self.h, self._p())
-        else:
+        if kv is None and not packed:
             q = Fn.linear(query, self.linear_q.weight, self.linear_q.bias)
             k = Fn.linear(key, self.linear_k.weight, self.linear_k.bias)
             v = Fn.linear(value, self.linear_v.weight, self.linear_v.bias)
-            ctx, self.attn = Fn.attention_core(q, k, v, kl, causal, self.h, self._p())
+            ctx, self.attn = FAttn.attention_core(q, k, v, kl, causal, self.h, p)
             qp = query
+        else:
+            # the packed projections: Q | K | V of the one input (self-attention), or Q here and K | V of the memory
+            qkv = kv is None and query is key
+            w_in, b_in = (f["w_qkv"], f["b_qkv"]) if qkv else (f["w_q"], f["b_q"])
+            if FAttn.attn_block_ok(query, (key if kv is None else kv).shape[1], kv, self.h, wo):
+                # short sequences, bf16, training: projection + core + out-projection as one autograd node (its backward folds the
+                # out-projection's data gradient into the core's launch)
+                if qkv:
+                    r = FAttn.attention_block_qkv(query, w_in, b_in, wo, bo, kl, causal, self.h, p, passthrough)
+                else:
+                    if kv is None:
+                        kv = Fn.linear(key, f["w_kv"], f["b_kv"])                       # ONE GEMM, N = 2D
+                    r = FAttn.attention_block_kv(query, w_in, b_in, kv, wo, bo, kl, causal, self.h, p, passthrough)
+                self.attn = r[1]
+                return (r[0], r[2]) if passthrough else r[0]
+            h = Fn.linear(query, w_in, b_in, passthrough=passthrough)                   # ONE GEMM, N = 3D or D
+            h, qp = h if passthrough else (h, None)
+            if qkv:
+                ctx, self.attn = FAttn.attention_packed_qkv(h, kl, causal, self.h, p)
+            else:
+                if kv is None:
+                    kv = Fn.linear(key, f["w_kv"], f["b_kv"])                           # ONE GEMM, N = 2D
+                ctx, self.attn = FAttn.attention_packed_kv(h, kv, kl, causal, self.h, p)
         out = Fn.linear(ctx, wo, bo)
         return (out, qp) if passthrough else out
 
@@ -420,17 +416,17 @@ class RelPositionMultiHeadedAttention(MultiHeadedAttention):
         if f is not None and "w_qkv" in f and query is key and key is value:
             qkv = Fn.linear(query, f["w_qkv"], f["b_qkv"])                              # ONE GEMM, N = 3D
             pos = Fn.linear(pos_emb, self.linear_pos.weight, None)
-            ctx, self.attn = Fn.rel_attention_packed(qkv, pos, self.pos_bias_u, self.pos_bias_v,
-                                                     None if klens is None else klens.dev, self.h, self._p(),
-                                                     2 if self.legacy else 1)
+            ctx, self.attn = FAttn.rel_attention_packed(qkv, pos, self.pos_bias_u, self.pos_bias_v,
+                                                        None if klens is None else klens.dev, self.h, self._p(),
+                                                        2 if self.legacy else 1)
             return Fn.linear(ctx, self.linear_out.weight, self.linear_out.bias)
         q = Fn.linear(query, self.linear_q.weight, self.linear_q.bias)
         k = Fn.linear(key, self.linear_k.weight, self.linear_k.bias)
         v = Fn.linear(value, self.linear_v.weight, self.linear_v.bias)
         pos = Fn.linear(pos_emb, self.linear_pos.weight, None)
-        qu, qv = Fn.add_head_bias(q, self.pos_bias_u, self.pos_bias_v)
-        ctx, self.attn = Fn.rel_attention_core(qu, qv, k, v, pos, None if klens is None else klens.dev, self.h, self._p(),
-                                               2 if self.legacy else 1)
+        qu, qv = FAttn.add_head_bias(q, self.pos_bias_u, self.pos_bias_v)
+        ctx, self.attn = FAttn.rel_attention_core(qu, qv, k, v, pos, None if klens is None else klens.dev, self.h, self._p(),
+                                                  2 if self.legacy else 1)
         return Fn.linear(ctx, self.linear_out.weight, self.linear_out.bias)
 
 
@@ -821,7 +817,7 @@ class Decoder(nn.Module):
             # the memory is projected for ALL layers by one GEMM (N = layers * 2D); backward: one dgrad GEMM with
             # K = layers * 2D instead of one per layer plus the gradient adds over the memory's fan-out
             kv_all = Fn.linear(memory, f["w"], f["b"])
-            per_layer = [{"kv": t} for t in Fn.split_cols(kv_all, len(self.decoders))]
+            per_layer = [{"kv": t} for t in FAttn.split_cols(kv_all, len(self.decoders))]
         if head is not None:
             per_layer = per_layer if per_layer is not None else [{} for _ in self.decoders]
             per_layer[0] = dict(per_layer[0], head=head)

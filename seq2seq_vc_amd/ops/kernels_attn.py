@@ -59,9 +59,9 @@ def fused_bwd(q, k, v, dout, attn, dattn, H, scale, p, seed, dq, dk_out, dv):
 # ----------------------------------------------------------------------------------------------
 # the fused backward with the out-projection's data gradient as its prologue (attn_proj_bwd_kernel)
 # ----------------------------------------------------------------------------------------------
-# S2SVC_NO_ATTN_PROJ (the switch: A/B against the separate launches): "1" = every fold off, "bwd" = the backward fold off;
-# "fwd" names the forward folds (Q / Q|K|V projection ahead of the fused forward), of which this build carries none
-_PROJ_OFF = {"0": set(), "1": {"fwd", "bwd"}, "fwd": {"fwd"}, "bwd": {"bwd"}}[os.environ.get("S2SVC_NO_ATTN_PROJ", "0")]
+# S2SVC_NO_ATTN_PROJ (the switch: A/B against the separate launches): "1" and "bwd" = the backward fold off
+# (the only fold this build carries; a set, so that a test can switch it by name)
+_PROJ_OFF = {"0": set(), "1": {"bwd"}, "bwd": {"bwd"}}[os.environ.get("S2SVC_NO_ATTN_PROJ", "0")]
 
 
 def proj_bwd_supported(dtype, T1, T2, dk, D):

@@ -173,6 +173,7 @@ def _block_run(kind, mode, inp, D, H, T1, T2, causal, p):
     """Outputs and gradients of one attention block on the wiring `mode`: "nodes" = Fn.linear -> Fn.attention_packed_* -> Fn.linear (the
     separate autograd nodes), "block" = the one-node block, "block_off" = the one-node block with the switch S2SVC_NO_ATTN_PROJ=bwd."""
     from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import functional_attn as FAttn
     n_in = 3 * D if kind == "self" else D
     x = inp["dy"].to(DEV).clone().requires_grad_(True)                                   # (B, T1, D) bf16 of unit scale
     w_in = R.randn(n_in, D, seed=901, scale=D ** -0.5).to(DEV).requires_grad_(True)
@@ -188,12 +189,12 @@ def _block_run(kind, mode, inp, D, H, T1, T2, causal, p):
     try:
         if mode == "nodes":
             h, xp = Fn.linear(x, w_in, b_in, passthrough=True)
-            cv, attn = (Fn.attention_packed_qkv(h, klen, causal, H, p) if kind == "self" else Fn.attention_packed_kv(h, mem, klen, causal, H, p))
+            cv, attn = (FAttn.attention_packed_qkv(h, klen, causal, H, p) if kind == "self" else FAttn.attention_packed_kv(h, mem, klen, causal, H, p))
             y = Fn.linear(cv, w_o, b_o)
         else:
-            assert Fn.attn_block_ok(x, T2, mem, H, w_o) == (mode == "block")
-            y, attn, xp = (Fn.attention_block_qkv(x, w_in, b_in, w_o, b_o, klen, causal, H, p, True) if kind == "self" else
-                           Fn.attention_block_kv(x, w_in, b_in, mem, w_o, b_o, klen, causal, H, p, True))
+            assert FAttn.attn_block_ok(x, T2, mem, H, w_o) == (mode == "block")
+            y, attn, xp = (FAttn.attention_block_qkv(x, w_in, b_in, w_o, b_o, klen, causal, H, p, True) if kind == "self" else
+                           FAttn.attention_block_kv(x, w_in, b_in, mem, w_o, b_o, klen, causal, H, p, True))
         gy, gx = R.randn(*y.shape, seed=904, dtype=BF16).to(DEV), R.randn(*x.shape, seed=905, dtype=BF16).to(DEV)
         ((y.float() * gy.float()).sum() + (attn.float() * inp["dattn"].to(DEV).float()).sum() + (xp.float() * gx.float()).sum()).backward()
     finally:

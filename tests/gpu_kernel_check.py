@@ -113,7 +113,7 @@ def gemm_epilogue_dropout_mask(dtype):
 def attention_fused_vs_reference():
     """Fused short-sequence attention (bf16): forward / backward vs fp32 torch math, and -- with dropout on -- vs the unfused
     kernels (same seed => same dropout masks), for self / causal / source attention on packed and separate projections."""
-    from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import functional_attn as FAttn
     from seq2seq_vc_amd.ops import kernels_attn as KAT
     res = []
     dt_ = torch.bfloat16
@@ -145,7 +145,7 @@ def attention_fused_vs_reference():
         assert KAT.supported(q, k, v, H), "shape should take the fused kernel"
         for use_datt, gref in ((False, g_plain), (True, g_att)):
             qf, kf, vf = (t.clone().requires_grad_(True) for t in (q, k, v))
-            out, att = Fn.attention_core(qf, kf, vf, klen, causal, H, 0.0)
+            out, att = FAttn.attention_core(qf, kf, vf, klen, causal, H, 0.0)
             loss = (out.float() * dy.float()).sum()
             if use_datt:
                 loss = loss + (att.float() * datt.float()).sum()
@@ -168,7 +168,7 @@ def attention_fused_vs_reference():
                 K.manual_seed(123)
                 K.reset_op_counter()
                 x = qkv.clone().requires_grad_(True)
-                o, a = Fn.attention_packed_qkv(x, kl2, causal, H, 0.3)
+                o, a = FAttn.attention_packed_qkv(x, kl2, causal, H, 0.3)
                 (o.float() * dy[:, :Tq].float()).sum().backward()
                 outs.append((o.detach(), a.detach(), x.grad.detach()))
             finally:
@@ -180,9 +180,9 @@ def attention_fused_vs_reference():
 
 @case
 def split_cols_block_consumed_twice():
-    """One column block of split_cols feeding TWO source-attention calls (no model does; Fn._GradSink hands every block's in-place
+    """One column block of split_cols feeding TWO source-attention calls (no model does; FAttn._GradSink hands every block's in-place
     view to its first consumer only): the block's gradient must be g1 + g2, as with plain slicing."""
-    from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import functional_attn as FAttn
     res = []
     B, H, T1, T2, dk = 2, 4, 40, 48, 96
     D = H * dk
@@ -194,10 +194,10 @@ def split_cols_block_consumed_twice():
     grads = []
     for use_split in (True, False):
         x = kv_all.clone().requires_grad_(True)
-        blocks = Fn.split_cols(x, 2) if use_split else (x[..., :2 * D], x[..., 2 * D:])
-        o1, _ = Fn.attention_packed_kv(q1, blocks[0], klen, False, H, 0.0)
-        o2, _ = Fn.attention_packed_kv(q2, blocks[0], klen, False, H, 0.0)        # block 0 a second time
-        o3, _ = Fn.attention_packed_kv(q1, blocks[1], klen, False, H, 0.0)
+        blocks = FAttn.split_cols(x, 2) if use_split else (x[..., :2 * D], x[..., 2 * D:])
+        o1, _ = FAttn.attention_packed_kv(q1, blocks[0], klen, False, H, 0.0)
+        o2, _ = FAttn.attention_packed_kv(q2, blocks[0], klen, False, H, 0.0)        # block 0 a second time
+        o3, _ = FAttn.attention_packed_kv(q1, blocks[1], klen, False, H, 0.0)
         ((o1.float() * dy1.float()).sum() + (o2.float() * dy2.float()).sum() + (o3.float() * dy3.float()).sum()).backward()
         grads.append(x.grad.detach().clone())
     res.append(check("split_cols block used twice: gradient == plain slicing", grads[0], grads[1], dt_, atol=2e-2, rtol=2e-2))

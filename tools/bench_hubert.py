@@ -63,6 +63,7 @@ def main():
 
     import hubert_ref as HR
     from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import functional_attn as FAttn
     from seq2seq_vc_amd.ops import kernels_hubert as KH
     from seq2seq_vc_amd.urhythmic import model as UM
     from seq2seq_vc_amd.urhythmic.hubert import HubertSoft
@@ -102,8 +103,8 @@ def main():
         out = torch.empty(1, T, D, dtype=torch.bfloat16, device=dev)
         with torch.no_grad():
             ours = measure(lambda: KH.attn_flash_fwd(q, k, v, H, None, out=out), a.repeats, a.target_s)
-            theirs = measure(lambda: Fn._attn_fwd_views(q, k, v, None, False, H, 0.0), a.repeats, a.target_s)
-            other = Fn._attn_fwd_views(q, k, v, None, False, H, 0.0)[0]
+            theirs = measure(lambda: FAttn._attn_fwd_views(q, k, v, None, False, H, 0.0), a.repeats, a.target_s)
+            other = FAttn._attn_fwd_views(q, k, v, None, False, H, 0.0)[0]
         res["attention"][f"T{T}_H{H}_dk64_bf16"] = {"flash": ours, "rival": rival, "rival_time": theirs, "speedup": theirs["ms_per_call"] / ours["ms_per_call"],
                                                     "verdict": verdict(ours, theirs), "max_abs_difference": float((out.float() - other.float()).abs().max())}
     line = json.dumps(res)
