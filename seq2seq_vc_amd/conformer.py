@@ -9,6 +9,7 @@ from torch import nn
 
 from . import modules as Mo
 from .ops import functional as Fn
+from .ops import schedule as Sched
 from .ops import functional_aas as FA
 
 
@@ -188,7 +189,7 @@ class ConformerEncoder(nn.Module):
         cut_name = getattr(self, "cut_name", None)      # data-parallel overlap: "<name>.<i>" cuts the graph at the input of layer i
         for li, layer in enumerate(self.encoders):
             if cut_name is not None and li > 0:
-                xs = Fn.cut_point(xs, f"{cut_name}.{li}")
+                xs = Sched.cut_point(xs, f"{cut_name}.{li}")
             xs = layer(xs, pos_emb, lens)
         if self.normalize_before:
             xs = self.after_norm(xs)

@@ -6,7 +6,7 @@ BatchNorm statistics stay rank-local and rank 0's buffers are what a checkpoint 
 
 Here the gradients already live in ONE flat fp32 buffer (optim.FlatAdam) that the weight-gradient kernels write into
 directly -- autograd never sees them, so there are no per-parameter hooks to hang a bucket on.  Instead the model names a
-few *gradient cuts* (ops.functional.cut_point) and a stage plan (`model.dp_plan()`): the backward pass runs stage by
+few *gradient cuts* (ops.schedule.cut_point) and a stage plan (`model.dp_plan()`): the backward pass runs stage by
 stage, every stage finishes the gradients of one contiguous range of the flat buffer, and that range's all-reduce is
 started (asynchronously, on RCCL's stream) before the next stage is launched:
 
@@ -30,7 +30,7 @@ import os
 
 import torch
 
-from ..ops import functional as Fn
+from ..ops import schedule as Sched
 
 
 def init_from_env(backend=None):
@@ -194,7 +194,7 @@ class OverlappedBackward:
         self.plan = plan if plan is not None else model.dp_plan()
         roots = [r for st in self.plan for r in ([st["root"]] if isinstance(st["root"], str) else st["root"])]
         roots += [st["branch_root"] for st in self.plan if st.get("branch_root")]
-        self.cuts = Fn.GradCuts([r[4:] for r in roots if r.startswith("cut:")])
+        self.cuts = Sched.GradCuts([r[4:] for r in roots if r.startswith("cut:")])
         self.ranges = [optimizer.param_ranges(st["modules"]) for st in self.plan]
         covered = sorted(r for rs in self.ranges for r in rs)
         pos = 0
@@ -213,7 +213,7 @@ class OverlappedBackward:
 
     # -- pieces ---------------------------------------------------------------------------------------------
     def forward_context(self):
-        return Fn.grad_cuts(self.cuts)
+        return Sched.grad_cuts(self.cuts)
 
     def active(self):
         return self.world > 1 or self.force
@@ -231,26 +231,26 @@ class OverlappedBackward:
         s = self.scale if scale is None else scale
         if branch_root is not None and branch_root.startswith("cut:"):      # the rest of a branch below a cut of an earlier stage
             if fork is not None:
-                Fn.branch_resume(self.cuts, branch_root[4:], fork)
+                Sched.branch_resume(self.cuts, branch_root[4:], fork)
             else:
                 self.cuts.resume(branch_root[4:])
         elif branch_root is not None:                            # first: the calling stream is still empty
             loss = losses.get(branch_root[5:])
             if loss is not None and loss.requires_grad:
                 if fork is not None:
-                    Fn.branch_backward(loss, fork, retain_graph=False, scale=s)
+                    Sched.branch_backward(loss, fork, retain_graph=False, scale=s)
                 else:
-                    Fn.root_backward(loss, s, retain_graph=False)
+                    Sched.root_backward(loss, s, retain_graph=False)
         for root in ([roots] if isinstance(roots, str) else list(roots)):
             if root.startswith("loss:"):
                 loss = losses.get(root[5:])
                 if loss is not None and loss.requires_grad:
-                    Fn.root_backward(loss, s, retain_graph=False)
+                    Sched.root_backward(loss, s, retain_graph=False)
             else:
                 self.cuts.resume(root[4:])
-        Fn.side_join()
+        Sched.side_join()
         if fork is not None:
-            Fn.branch_wait()
+            Sched.branch_wait()
 
     def mark(self, i):
         """Record "stage i's gradients are final" on the current stream.  Inside a capture this is an event-record NODE of the
@@ -273,7 +273,7 @@ class OverlappedBackward:
             return
         if after_mark and i in self.marks:
             if self.comm_stream is None:
-                self.comm_stream = Fn.distinct_stream()
+                self.comm_stream = Sched.distinct_stream()
             self.marks[i].wait(self.comm_stream)
             with torch.cuda.stream(self.comm_stream):
                 self._begin_reduce(i)
@@ -327,7 +327,7 @@ class FlushExchange:
     OverlappedBackward cuts the backward pass into stages; every cut is a join of the parameter-gradient work (and of the branch on
     the auxiliary stream), and those joins -- not the graph boundaries: one graph with event-record nodes costs the same as one
     graph per stage -- are what a finer plan pays for (AAS-VC with a stage per decoder layer: 12.7 vs 10.8 ms).  Here nothing is
-    cut.  The parameter-gradient closures of a backward pass are flushed in batches anyway (ops.functional._side_run); behind every
+    cut.  The parameter-gradient closures of a backward pass are flushed in batches anyway (ops.schedule._side_run); behind every
     flush a mark is recorded on the flushing stream (ops.kernels.GraphMark: an event-record node when the step is captured), and the
     slices of the flat gradient buffer that are FINAL at a flush -- learned once, from an instrumented eager pass that snapshots the
     buffer behind every flush -- are all-reduced from the communication stream behind that mark, while the same graph keeps running
@@ -393,10 +393,10 @@ class FlushExchange:
         class _Ctx:
             def __enter__(self_):
                 fx.mode, fx.n = "mark", 0
-                Fn._Side.on_flush = fx._on_flush
+                Sched.set_on_flush(fx._on_flush)
 
             def __exit__(self_, *exc):
-                Fn._Side.on_flush = None
+                Sched.set_on_flush(None)
                 fx.mode = None
                 if exc[0] is None and fx.plan is not None and fx.n != fx.n_flushes:
                     raise RuntimeError(f"FlushExchange: this pass flushed {fx.n} gradient batches, the learned plan has {fx.n_flushes} "
@@ -404,7 +404,7 @@ class FlushExchange:
         return _Ctx()
 
     def mark_end(self):
-        """Behind the join of the backward pass (ops.functional.side_join) on the current stream: everything is final."""
+        """Behind the join of the backward pass (ops.schedule.side_join) on the current stream: everything is final."""
         if not self.active():
             return
         from ..ops import kernels as K
@@ -419,7 +419,7 @@ class FlushExchange:
         try:
             run()
         finally:
-            Fn._Side.on_flush = None
+            Sched.set_on_flush(None)
             self.mode = None
         return self.learn_end()
 
@@ -445,11 +445,11 @@ class FlushExchange:
         torch.cuda.synchronize()
         self.snap = opt.flat_g.clone()          # zeros, or what earlier micro-steps of an accumulation window left
         self.mode, self.n = "learn", 0
-        Fn._Side.on_flush = self._on_flush
+        Sched.set_on_flush(self._on_flush)
         self._los, self._his = los, his
 
     def learn_end(self):
-        Fn._Side.on_flush = None
+        Sched.set_on_flush(None)
         self.mode = None
         los, his = self._los, self._his
         torch.cuda.synchronize()
@@ -505,7 +505,7 @@ class FlushExchange:
             raise RuntimeError("FlushExchange.issue() before learn()")
         from ..ops import kernels as K
         if self.comm_stream is None:
-            self.comm_stream = Fn.distinct_stream()
+            self.comm_stream = Sched.distinct_stream()
         comm = self.comm_stream
         for n, ranges in self.plan:
             if n is None:

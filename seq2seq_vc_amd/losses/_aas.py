@@ -45,13 +45,13 @@ class ForwardSumLoss(torch.nn.Module):
     def prefetch(self, log_p_attn, ilens, olens, blank_prob: float = math.e ** -1):
         """Hook for the model (AASVC.forward_sum_prefetch, set by the trainers): called in the training forward pass as soon as
         the alignment module has produced `log_p_attn`.  The alpha recursion is T_feats dependent steps on one wavefront per
-        utterance (~150 us that leave the chip empty); here it runs on the auxiliary stream (ops.functional.branch_run) beside
+        utterance (~150 us that leave the chip empty); here it runs on the auxiliary stream (ops.schedule.branch_run) beside
         the length regulator / decoder instead of after them, and forward() picks the result up from the tensor when it is
         called with the same lengths.  The model's branch_join covers it."""
         dev = log_p_attn.device
         if dev.type != "cuda" or os.environ.get("S2SVC_FS_PREFETCH", "1") == "0":       # (A/B aid)
             return
-        from ..ops import functional as Fn
+        from ..ops import schedule as Sched
         il, ol = Lens.of(ilens, dev), Lens.of(olens, dev)
         _, Tf, Tx = log_p_attn.shape
         lp = log_p_attn.detach()
@@ -59,7 +59,7 @@ class ForwardSumLoss(torch.nn.Module):
         def run():
             return KA.forward_sum(lp.float().contiguous(), self._prior(il, ol, Tf, Tx, dev), il.dev, ol.dev, blank_prob)
 
-        loss_b, grad = Fn.branch_run(run, uses=(lp, il.dev, ol.dev))
+        loss_b, grad = Sched.branch_run(run, uses=(lp, il.dev, ol.dev))
         log_p_attn._s2s_fs = (loss_b, grad, il.dev.data_ptr(), ol.dev.data_ptr(), blank_prob)
 
 

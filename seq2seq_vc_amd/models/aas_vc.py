@@ -14,6 +14,7 @@ from torch import nn
 from .. import modules as Mo
 from ..conformer import ConformerEncoder
 from ..ops import functional as Fn
+from ..ops import schedule as Sched
 from ..ops import functional_aas as FA
 from ..sdp import DurationPredictor, StochasticDurationPredictor
 
@@ -165,7 +166,7 @@ class AASVC(nn.Module):
         parameters of the vc2 configuration (4 layers x 28 M at d = 1536).  Two loss keys: "decoder" (the L1 loss: reaches the
         postnet / decoder / length regulator) and "align" (forward-sum + binarisation + duration losses: reach the alignment
         module and the duration predictor); below the cut at the encoder output both meet and the encoder runs last.
-        Stage 1 runs BOTH roots: first "align", rooted on the auxiliary stream (`branch_root`, ops.functional.branch_backward:
+        Stage 1 runs BOTH roots: first "align", rooted on the auxiliary stream (`branch_root`, ops.schedule.branch_backward:
         the duration branch -- input projection + predictor -- ran there in the forward pass, so its whole backward pass runs
         there; the main stream only gets the short alignment-module part), then "decoder" down to the encoder output on the
         calling stream, beside it; the stage ends with the join.  Stage 2 is the encoder.
@@ -231,9 +232,9 @@ class AASVC(nn.Module):
         f_pre = None
         if not is_inference and ys is not None and xs.is_cuda and _FBRANCH:
             # the alignment module's feature side needs nothing from the encoder: auxiliary stream, beside it (forward and backward)
-            f_pre = Fn.branch_run(lambda: self.alignment_module.feats_branch(Fn.to_compute(ys), olr), uses=(ys,))
+            f_pre = Sched.branch_run(lambda: self.alignment_module.feats_branch(Fn.to_compute(ys), olr), uses=(ys,))
         hs, _ = self.encoder(Fn.to_compute(xs), il)
-        hs = Fn.cut_point(hs, "encoder_out")
+        hs = Sched.cut_point(hs, "encoder_out")
         if self.encoder_input_layer == "conv2d":
             il = il.map(lambda v: ((v - 2 + 1) // 2 - 2 + 1) // 2)
         if pr > 1:
@@ -293,7 +294,7 @@ class AASVC(nn.Module):
             dec_lens = None
         else:
             if f_pre is not None:
-                Fn.branch_join(f_pre)
+                Sched.branch_join(f_pre)
                 log_p_attn = self.alignment_module(hs_al, None, il_c, f=f_pre)
             else:
                 log_p_attn = self.alignment_module(hs_al, Fn.to_compute(ys), il_c, feat_lens=olr)
@@ -306,7 +307,7 @@ class AASVC(nn.Module):
                 # ~330 small launches that depend on nothing the length regulator / decoder / postnet below produce: they
                 # run on the auxiliary stream beside them (forward here, backward through autograd's stream rule)
                 # (normalize: / the number of non-pad text positions, aas_vc.py:403, inside the NLL kernel)
-                ret["dur_nll"] = Fn.branch_run(lambda: self.duration_predictor.forward_cl(dp_input(), il_c, w=ds, normalize=True),
+                ret["dur_nll"] = Sched.branch_run(lambda: self.duration_predictor.forward_cl(dp_input(), il_c, w=ds, normalize=True),
                                                uses=(ds, hs, dp_inputs, il_c.dev))
             else:
                 d_outs = self.duration_predictor(dpi, il_c)
@@ -323,7 +324,7 @@ class AASVC(nn.Module):
             post_lens = dec_lens if dr == 1 else dec_lens.map(lambda v, _r=dr: v * _r)
         after = before if self.postnet is None else Fn.add_dropout(b_res, self.postnet(b_post, post_lens), 0.0)
         ret["before_outs"], ret["after_outs"] = before, after
-        Fn.branch_join(ret.get("dur_nll"), *(getattr(log_p_attn, "_s2s_fs", None) or ())[:2])
+        Sched.branch_join(ret.get("dur_nll"), *(getattr(log_p_attn, "_s2s_fs", None) or ())[:2])
         ret["ds"] = ds
         ret["ilens"] = Mo.tag_lens(self._lens_like(ilens, il.host), il)
         ret["bin_loss"] = bin_loss

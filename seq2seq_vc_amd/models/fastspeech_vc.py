@@ -18,6 +18,7 @@ from torch import nn
 from .. import modules as Mo
 from ..conformer import ConformerEncoder
 from ..ops import functional as Fn
+from ..ops import schedule as Sched
 from ..ops import functional_aas as FA
 from ..sdp import DurationPredictor
 
@@ -143,7 +144,7 @@ class FastSpeechVC(nn.Module):
             xs = xs.contiguous().view(b, tmax // er, dim * er)
             il = il.map(lambda v: v // er)
         hs, _ = self.encoder(Fn.to_compute(xs), il)
-        hs = Fn.cut_point(hs, "encoder_out")
+        hs = Sched.cut_point(hs, "encoder_out")
         if self.encoder_input_layer == "conv2d":        # (:279-280; the Transformer encoder's front-end does not adjust ilens)
             il = il.map(lambda v: ((v - 2 + 1) // 2 - 2 + 1) // 2)
         if self.duration_predictor_use_encoder_outputs:

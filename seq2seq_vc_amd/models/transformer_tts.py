@@ -7,6 +7,7 @@ from torch import nn
 
 from .. import modules as Mo
 from ..ops import functional as Fn
+from ..ops import schedule as Sched
 from ..ops import kernels as K
 from .vtn import _ARSeq2Seq
 
@@ -56,7 +57,7 @@ class TransformerTTS(_ARSeq2Seq):
         il1 = il.map(lambda v: v + 1)
         pre = self._decoder_head(ys, olens)
         hs, hs_lens = self.encoder(xs, il1)
-        hs = Fn.cut_point(hs, "encoder_out")
+        hs = Sched.cut_point(hs, "encoder_out")
         after, before, logits, ys_, labels_, olens_, olens_in = self._teacher_forced(hs, hs_lens, ys, labels, olens, pre=pre)
         att_ws = []
         if self.use_guided_attn_loss:

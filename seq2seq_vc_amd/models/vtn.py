@@ -11,6 +11,7 @@ from torch import nn
 
 from .. import modules as Mo
 from ..ops import functional as Fn
+from ..ops import schedule as Sched
 from ..ops import kernels as K
 
 
@@ -90,7 +91,7 @@ class _ARSeq2Seq(nn.Module):
                 lab = self._stop_labels(labels, olens_h)[1] if labels is not None else None
                 return y0, lab, self.decoder.head(Fn.to_compute(y0), olens_in_h, causal=True)
 
-            ys_in, stop, head = Fn.branch_run(run, uses=(ys, labels, olens_in_h.dev, olens_h.dev))
+            ys_in, stop, head = Sched.branch_run(run, uses=(ys, labels, olens_in_h.dev, olens_h.dev))
         else:
             ys_in = shifted()
         return olens_h, olens_in_h, ys_in, head, stop
@@ -110,11 +111,11 @@ class _ARSeq2Seq(nn.Module):
         r, odim = self.decoder_reduction_factor, self.odim
         olens_h, olens_in_h, ys_in, head, stop = pre if pre is not None else self._decoder_head(ys, olens)
         if head is not None:
-            Fn.branch_join(*head, ys_in, stop)
+            Sched.branch_join(*head, ys_in, stop)
             # gradient cut for the staged (data-parallel) backward pass: the head's backward pass -- the last thing of the decoder's,
             # on the auxiliary stream -- overlaps the encoder's in the one-graph step; a stage plan may run it in the encoder's stage
             # (dp_plan).  Identity outside distributed.OverlappedBackward.
-            head = Fn.cut_point(tuple(head), "decoder_head")
+            head = Sched.cut_point(tuple(head), "decoder_head")
             zs, _ = self.decoder(None, olens_in_h, hs, hs_lens, causal=True, head=head)
         else:
             zs, _ = self.decoder(Fn.to_compute(ys_in), olens_in_h, hs, hs_lens, causal=True)
@@ -137,9 +138,9 @@ class _ARSeq2Seq(nn.Module):
             # the stop-token projection (384 -> r columns: a GEMM with one output column forward, a rank-1 product backward, both on
             # slow general kernels) beside the Postnet instead of in front of it: the auxiliary stream is idle here, and autograd runs
             # its backward node there too -- beside the Postnet's backward pass instead of between it and feat_out's
-            (logits,) = Fn.branch_run(lambda: (Fn.linear(zs, self.prob_out.weight, self.prob_out.bias).view(zs.size(0), -1),), uses=(zs,))
+            (logits,) = Sched.branch_run(lambda: (Fn.linear(zs, self.prob_out.weight, self.prob_out.bias).view(zs.size(0), -1),), uses=(zs,))
             after = Fn.add_dropout(b_res, self.postnet(b_post, post_lens), 0.0)
-            Fn.branch_join(logits)
+            Sched.branch_join(logits)
         else:
             logits = Fn.linear(zs, self.prob_out.weight, self.prob_out.bias).view(zs.size(0), -1)
             after = Fn.add_dropout(b_res, self.postnet(b_post, post_lens), 0.0) if self.postnet is not None else before
@@ -277,7 +278,7 @@ class VTN(_ARSeq2Seq):
             ys, labels = ys[:, : ol.max()], labels[:, : ol.max()]
         pre = self._decoder_head(ys, olens, labels if self.decoder_reduction_factor > 1 else None)
         hs, hs_lens = self.encoder(Fn.to_compute(xs), il)
-        hs = Fn.cut_point(hs, "encoder_out")      # data-parallel overlap: decoder-side gradients travel during the encoder's backward
+        hs = Sched.cut_point(hs, "encoder_out")      # data-parallel overlap: decoder-side gradients travel during the encoder's backward
         after, before, logits, ys_, labels_, olens_, olens_in = self._teacher_forced(hs, hs_lens, ys, labels, olens, pre=pre)
         il_ds = il.map(lambda v: ((v - 2 + 1) // 2 - 2 + 1) // 2)
         ilens_ds_st = Mo.tag_lens(torch.tensor(list(il_ds.host), dtype=ilens.dtype if isinstance(ilens, torch.Tensor) else torch.long,

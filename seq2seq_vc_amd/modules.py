@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from .ops import functional as Fn
+from .ops import schedule as Sched
 from .ops import functional_attn as FAttn
 from .ops import kernels as K
 
@@ -593,7 +594,7 @@ def run_stack(layers, x, after_norm, pre_ln, dropout_rate, training, *args, per_
     for li, layer in enumerate(layers):
         kwl = dict(kw, **per_layer[li]) if per_layer is not None else kw      # this layer's own extras only
         if cut_name is not None and li > 0:
-            x, pending = Fn.cut_point((x, pending), f"{cut_name}.{li}")
+            x, pending = Sched.cut_point((x, pending), f"{cut_name}.{li}")
         if pre_ln and pending is not None:
             normed, x = _res_norm(layer.norm1, x, pending, p)
             x, pending = layer(x, *args, normed=normed, **kwl)
@@ -768,7 +769,7 @@ class TransformerEncoder(nn.Module):
             xs = self.embed[1](xs)
         cut_name = getattr(self, "cut_name", None)      # data-parallel overlap (models' dp_plan): cut behind the input layer
         if cut_name is not None:
-            xs = Fn.cut_point(xs, f"{cut_name}.0")
+            xs = Sched.cut_point(xs, f"{cut_name}.0")
         xs = run_stack(self.encoders, xs, getattr(self, "after_norm", None), self.normalize_before, self.dropout_rate,
                        self.training, lens, cut_name=cut_name)
         return xs, lens

@@ -4,7 +4,8 @@ from torch.autograd import Function
 
 from . import kernels as K
 from . import kernels_aas as KA
-from .functional import _c, _emit_vgrad, _reduce_to, _side_run, _slotted
+from .functional import _c, _emit_vgrad, _reduce_to, _slotted
+from .schedule import _side_run
 
 
 class _DwConv(Function):
@@ -179,11 +180,10 @@ class _PairwiseLogSoftmax(Function):
         # dtext[b,j,:] = text[b,j,:]*sum_i G[b,i,j] - sum_i G[b,i,j] feats[b,i,:]
         # column sums over the frame axis, one deterministic reduction per utterance: all of them as ONE grouped launch pair
         cs = K.zeros((B, Tx), torch.float32, feats.device)
-        queue = []
-        with K.record_colreduce(queue):
+        with K.recording(K.GradBatch()) as sums:
             for b in range(B):
                 K.colreduce(0, G[b], out_sum=cs[b], accumulate=True)
-        K.flush_colreduce(queue)
+        sums.flush()
         r2 = KA.rowscale(text, cs.view(-1))
         dtx = torch.empty_like(text)
         K.gemm(K.operand(G, Tx, layout=K.RC, bs0=Tf * Tx), K.operand(feats, A, layout=K.RC, bs0=Tf * A), Tx, A, Tf, dtx,

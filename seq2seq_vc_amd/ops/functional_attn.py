@@ -12,7 +12,8 @@ from torch.autograd import Function
 
 from . import kernels as K
 from . import kernels_attn as KAT
-from .functional import _c, _linear_bwd, _reduce_to, _side_run, _slotted, _wcast
+from .functional import _c, _linear_bwd, _reduce_to, _slotted, _wcast
+from .schedule import _side_run
 
 
 # ================================================================================================

@@ -15,7 +15,8 @@ from torch.autograd import Function
 
 from . import kernels as K
 from . import kernels_sdp as KS
-from .functional import _c, _emit_vgrad, _reduce_to, _side_run, _slotted
+from .functional import _c, _emit_vgrad, _reduce_to, _slotted
+from .schedule import _side_run
 
 
 _QUEUE_LN = True        # LayerNorm parameter gradients of the duration predictor join the grouped column reductions of their batch

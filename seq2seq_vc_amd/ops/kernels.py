@@ -328,7 +328,7 @@ class GraphMark:
 # eager launches hide (the GPU happens to keep issue order) and a captured graph exposes (only edges order its branches) --
 # the signature of round 3's "second side stream" experiment, whose gradient norm moved under capture only.  With the audit on,
 # every accumulating launch records (slot pointer -> stream); a second writer from another stream raises unless a join
-# (ops.functional.side_join) came in between.
+# (ops.schedule.side_join) came in between.
 # ----------------------------------------------------------------------------------------------
 class _Audit:
     on = os.environ.get("S2SVC_AUDIT_SLOTS", "0") == "1"
@@ -419,7 +419,7 @@ def gemm(A, B, M, N, K, out, *, in_dtype, bias=None, act=None, res=None, ldr=Non
     # accumulate, ops.functional._LinearPermuted) read its buffer before the GEMM had run -- found by the full-size gradient
     # test of round 3 (tests/gpu_model_check.py: vtn_full_size_grads); steady-state training had been using the buffer's
     # previous contents, i.e. the gradient of the step before.
-    if _RECORDER is not None and accumulate:
+    if _BATCH is not None and accumulate:
         d.splitk, d.ws = 1, None
         if a_rowsum is not None:
             d.a_rowsum = a_rowsum.data_ptr()
@@ -430,7 +430,7 @@ def gemm(A, B, M, N, K, out, *, in_dtype, bias=None, act=None, res=None, ldr=Non
         # them: AAS-VC step 14.57 -> 14.33 ms
         tiles8 = M % 256 == 0 and N % 256 == 0 and K % 64 == 0
         if (tiles8 or ((M + 127) // 128) * ((N + 127) // 128) < _GROUP_MAX_TILES) and _lib.lib().s2svc_gemm_grouped_ok(ctypes.addressof(d)):
-            _RECORDER.append(d)
+            _BATCH.gemms.append(d)
             return out
         d.splitk, d.a_rowsum = splitk, None
     if (accumulate or wgrad) and in_dtype == torch.bfloat16 and group is None:
@@ -470,72 +470,101 @@ def gemm(A, B, M, N, K, out, *, in_dtype, bias=None, act=None, res=None, ldr=Non
 
 
 # ----------------------------------------------------------------------------------------------
-# Grouped weight-gradient GEMMs: while a recorder is active, eligible GEMMs (bf16, both operands dense and
-# row-contiguous, i.e. dW = dY^T X) are queued instead of launched; flush_grouped() runs the queue as ONE grid per
-# <= 11 problems (s2svc_gemm_grouped).  The caller keeps the operand tensors alive until the flush.
+# Gradient batches.  While a GradBatch is the active one (`with recording(batch)`), three kinds of parameter-gradient launches are
+# queued on it instead of launched: eligible weight-gradient GEMMs (bf16, both operands dense and row-contiguous, i.e.
+# dW = dY^T X; K.gemm), accumulating column reductions (K.colreduce / colreduce_partials) and Conv1d weight gradients
+# (conv1d_wgrad_queue).  batch.flush() runs the three queues on the current stream: ONE grid per <= 11 GEMMs
+# (s2svc_gemm_grouped; <= 40 on the 8-wave kernel), two launches per <= 24 reductions, one per <= 16 Conv1d layers.  The caller
+# keeps the operand tensors alive until the flush.
 # ----------------------------------------------------------------------------------------------
-_RECORDER = None            # list of GemmDesc while recording
+_BATCH = None                # the active GradBatch
 _GROUP_TILE = 64             # output tile edge of the grouped kernel for small outputs
 _GROUP_MAX_TILES = 200
 _GROUP_BIG_TILES = 64
 
 
-class record_grouped:
-    """with record_grouped(queue): K.gemm(...) appends eligible problems to `queue` (list) instead of launching."""
-
-    def __init__(self, queue):
-        self.queue = queue
-
-    def __enter__(self):
-        global _RECORDER
-        self.prev, _RECORDER = _RECORDER, self.queue
-        return self.queue
-
-    def __exit__(self, *exc):
-        global _RECORDER
-        _RECORDER = self.prev
-        return False
-
-
-_CR_RECORDER = None         # list of (ColreduceItem, keepalive) while recording
-
-
-class record_colreduce:
-    """with record_colreduce(queue): accumulating K.colreduce(...) calls are queued instead of launched."""
-
-    def __init__(self, queue):
-        self.queue = queue
-
-    def __enter__(self):
-        global _CR_RECORDER
-        self.prev, _CR_RECORDER = _CR_RECORDER, self.queue
-        return self.queue
-
-    def __exit__(self, *exc):
-        global _CR_RECORDER
-        _CR_RECORDER = self.prev
-        return False
-
-
-def flush_colreduce(queue):
-    """Launch the queued column reductions on the current stream, two launches per <= 24 of them; reductions into the same
-    output go to successive launches.  Empties the queue."""
-    pending = list(queue)
-    del queue[:]
+def disjoint_waves(items, writes):
+    """Yield `items` as successive lists ("waves") whose members write disjoint outputs; writes(item) -> the set of addresses
+    the item writes.  Every pass over what is left takes, in order, each item that shares no address with those already taken."""
+    pending = list(items)
     while pending:
-        seen, group, rest = set(), [], []
-        for it, keep in pending:
-            keys = {it.out_sum} | ({it.out_dot} if it.out_dot else set())
+        seen, wave, rest = set(), [], []
+        for it in pending:
+            keys = writes(it)
             if keys & seen:
-                rest.append((it, keep))
+                rest.append(it)
             else:
                 seen |= keys
-                group.append((it, keep))
+                wave.append(it)
         pending = rest
-        arr = (_lib.ColreduceItem * len(group))(*[g[0] for g in group])
-        if _Audit.on:
-            _audit_write("grouped column reduction", *[g[0].out_sum for g in group], *[g[0].out_dot for g in group])
-        _lib.check(_lib.lib().s2svc_colreduce_grouped(ctypes.addressof(arr), len(group), stream()), "s2svc_colreduce_grouped")
+        yield wave
+
+
+class GradBatch:
+    """What one batch of gradient closures queues (ops.schedule._run_batch), and the workgroup cap of its grouped weight-gradient
+    launches (GEMMs and Conv1d): 0 = one workgroup per unit; a batch forked beside the data-gradient chain is capped
+    (ops.schedule._FORK_CAP).  Units are walked in order: the cap does not change a bit of the results."""
+
+    def __init__(self, cap=0):
+        self.gemms = []          # GemmDesc
+        self.colreduces = []     # (ColreduceItem, keepalive)
+        self.conv1d = []         # (dy, x, dw)
+        self.cap = max(0, int(cap))
+
+    def flush(self):
+        """Launch what is queued on the current stream -- GEMMs, column reductions, Conv1d weight gradients -- and empty the queues.
+        Items of one queue that would write the same output concurrently go to successive launches."""
+        gemms, colreduces, conv1d = self.gemms, self.colreduces, self.conv1d
+        self.gemms, self.colreduces, self.conv1d = [], [], []
+        with recording(self):                # launch_wgrad_group reads the active batch's cap
+            for group in disjoint_waves(gemms, lambda d: {d.C} | ({d.a_rowsum} if d.a_rowsum else set())):
+                # ragged dense weight gradients (any M, N % 8 == 0: VTN's 384 / 1152 / 1536-feature layers): the 8-wave kernel on (problem,
+                # K chunk, 256 x 128 tile) units (csrc/gemm_8ph.hip "W8"); WHICH kernel a problem gets depends on its descriptor only
+                L = _lib.lib()
+                w8 = [d for d in group if L.s2svc_gemm_wgrad_ok(ctypes.addressof(d))]
+                if w8:
+                    group = [d for d in group if not any(d is w for w in w8)]
+                    if _Audit.on:
+                        _audit_write("grouped weight gradient (W8)", *[d.C for d in w8], *[d.a_rowsum for d in w8])
+                    launch_wgrad_group(w8)
+                # big outputs (>= _GROUP_BIG_TILES 128x128 tiles each) share launches of 128x128 tiles, the rest of 64x64 tiles
+                big = [d for d in group if _GROUP_TILE == 64 and ((d.M + 127) // 128) * ((d.N + 127) // 128) >= _GROUP_BIG_TILES]
+                small = [d for d in group if not any(d is b for b in big)]
+                for part, tile in ((big, 128), (small, _GROUP_TILE)):
+                    if part:
+                        arr = (_lib.GemmDesc * len(part))(*part)
+                        if _Audit.on:
+                            _audit_write("grouped weight gradient", *[d.C for d in part], *[d.a_rowsum for d in part])
+                        _lib.check(_lib.lib().s2svc_gemm_grouped(ctypes.addressof(arr), len(part), tile, stream()), "s2svc_gemm_grouped")
+            for wave in disjoint_waves(colreduces, lambda g: {g[0].out_sum} | ({g[0].out_dot} if g[0].out_dot else set())):
+                arr = (_lib.ColreduceItem * len(wave))(*[g[0] for g in wave])
+                if _Audit.on:
+                    _audit_write("grouped column reduction", *[g[0].out_sum for g in wave], *[g[0].out_dot for g in wave])
+                _lib.check(_lib.lib().s2svc_colreduce_grouped(ctypes.addressof(arr), len(wave), stream()), "s2svc_colreduce_grouped")
+            if conv1d:
+                conv1d_wgrad_grouped(conv1d, self.cap)
+
+
+class recording:
+    """with recording(batch): `batch` is the active GradBatch (the one before it again on exit)."""
+
+    def __init__(self, batch):
+        self.batch = batch
+
+    def __enter__(self):
+        global _BATCH
+        self.prev, _BATCH = _BATCH, self.batch
+        return self.batch
+
+    def __exit__(self, *exc):
+        global _BATCH
+        _BATCH = self.prev
+        return False
+
+
+def in_capped_batch():
+    """True while the active batch is a forked, capped one."""
+    return _BATCH is not None and _BATCH.cap > 0
 
 
 def launch_group(descs, tile=128):
@@ -544,32 +573,18 @@ def launch_group(descs, tile=128):
     _lib.check(_lib.lib().s2svc_gemm_grouped(ctypes.addressof(arr), len(descs), tile, stream()), "s2svc_gemm_grouped")
 
 
-_W8_CAP = [0]
-
-
-def set_wgrad_cap(wgs):
-    """Workgroups of a grouped weight-gradient launch on the current stream (0 = one per unit).  ops.functional.enable_side_streams
-    sets 64 for FORKED gradient batches (VTN / TTS): the launch runs beside the latency-bound data-gradient chain, and a 144 KB-LDS
-    workgroup on every CU makes each small kernel of the chain wait for one -- measured 3.789 -> 3.773 ms per VTN step (five
-    interleaved repeats; 48 / 96 / 128 workgroups: 3.778 / 3.774 / 3.780).  Units are walked in order: bit-identical results."""
-    _W8_CAP[0] = max(0, int(wgs))
-
-
-def get_wgrad_cap():
-    return _W8_CAP[0]
-
-
 def launch_wgrad_group(descs, capped=True):
     """The listed weight-gradient problems (every one s2svc_gemm_wgrad_ok) on the ragged 8-wave kernel, one grid per <= 40 of
     them (+ one reduction launch when a reduction is long enough to be cut into chunks: its partial tiles go through `ws`).
-    capped=False: a chip-filling problem launched on its own (the front-end's Conv2d / Linear weight gradients) ignores the cap."""
+    A launch under a capped active batch (GradBatch.cap) takes at most that many workgroups; capped=False: a chip-filling problem
+    launched on its own (the front-end's Conv2d / Linear weight gradients) ignores the cap."""
     L = _lib.lib()
     arr = (_lib.GemmDesc * len(descs))(*descs)
     nws = L.s2svc_gemm_wgrad_ws_floats(ctypes.addressof(arr), len(descs))
     ws = torch.empty(nws, dtype=torch.float32, device=torch.cuda.current_device()) if nws else None
-    if capped and _W8_CAP[0] > 0:        # forked gradient batches: a capped grid leaves CUs to the chain the launch runs beside (set_wgrad_cap)
-        _lib.check(L.s2svc_gemm_wgrad_grouped_bg(ctypes.addressof(arr), len(descs), ptr(ws), stream(), _W8_CAP[0]),
-                   "s2svc_gemm_wgrad_grouped_bg")
+    cap = _BATCH.cap if capped and _BATCH is not None else 0
+    if cap > 0:        # forked gradient batches: a capped grid leaves CUs to the chain the launch runs beside (ops.schedule._FORK_CAP)
+        _lib.check(L.s2svc_gemm_wgrad_grouped_bg(ctypes.addressof(arr), len(descs), ptr(ws), stream(), cap), "s2svc_gemm_wgrad_grouped_bg")
         return
     _lib.check(L.s2svc_gemm_wgrad_grouped(ctypes.addressof(arr), len(descs), ptr(ws), stream()), "s2svc_gemm_wgrad_grouped")
 
@@ -590,66 +605,11 @@ def launch_group_batched(descs):
         _lib.check(_lib.lib().s2svc_gemm(ctypes.byref(d), stream()), "s2svc_gemm")
 
 
-def flush_grouped(queue):
-    """Launch every queued problem on the current stream; problems that would write the same C / a_rowsum concurrently
-    go to successive launches.  Empties the queue."""
-    pending = list(queue)
-    del queue[:]
-    while pending:
-        seen, group, rest = set(), [], []
-        for d in pending:
-            keys = {d.C} | ({d.a_rowsum} if d.a_rowsum else set())
-            if keys & seen:
-                rest.append(d)
-            else:
-                seen |= keys
-                group.append(d)
-        pending = rest
-        # ragged dense weight gradients (any M, N % 8 == 0: VTN's 384 / 1152 / 1536-feature layers): the 8-wave kernel on (problem,
-        # K chunk, 256 x 128 tile) units (csrc/gemm_8ph.hip "W8"); WHICH kernel a problem gets depends on its descriptor only
-        L = _lib.lib()
-        w8 = [d for d in group if L.s2svc_gemm_wgrad_ok(ctypes.addressof(d))]
-        if w8:
-            group = [d for d in group if not any(d is w for w in w8)]
-            if _Audit.on:
-                _audit_write("grouped weight gradient (W8)", *[d.C for d in w8], *[d.a_rowsum for d in w8])
-            launch_wgrad_group(w8)
-        # big outputs (>= _GROUP_BIG_TILES 128x128 tiles each) share launches of 128x128 tiles, the rest of 64x64 tiles
-        big = [d for d in group if _GROUP_TILE == 64 and ((d.M + 127) // 128) * ((d.N + 127) // 128) >= _GROUP_BIG_TILES]
-        small = [d for d in group if not any(d is b for b in big)]
-        for part, tile in ((big, 128), (small, _GROUP_TILE)):
-            if part:
-                arr = (_lib.GemmDesc * len(part))(*part)
-                if _Audit.on:
-                    _audit_write("grouped weight gradient", *[d.C for d in part], *[d.a_rowsum for d in part])
-                _lib.check(_lib.lib().s2svc_gemm_grouped(ctypes.addressof(arr), len(part), tile, stream()), "s2svc_gemm_grouped")
-
-
 # ----------------------------------------------------------------------------------------------
-# Conv1d weight gradients of a gradient batch (csrc/conv1d_wgrad.hip): while a recorder is active, ops.functional queues
-# (dy, x, dw) triples instead of launching split-K GEMM + reduction + permutation per layer; flush_conv1d_wgrad() runs the
+# Conv1d weight gradients of a gradient batch (csrc/conv1d_wgrad.hip): while a batch is active, ops.functional queues
+# (dy, x, dw) triples instead of launching split-K GEMM + reduction + permutation per layer; the batch's flush runs the
 # queue as ONE capped launch that adds straight into the (Cout, Cin, ks) gradient slots.
 # ----------------------------------------------------------------------------------------------
-_C1W_RECORDER = None        # list of (dy, x, dw) while recording
-
-
-class record_conv1d_wgrad:
-    """with record_conv1d_wgrad(queue): conv1d_wgrad_queue(...) appends to `queue` (list); without one it answers False."""
-
-    def __init__(self, queue):
-        self.queue = queue
-
-    def __enter__(self):
-        global _C1W_RECORDER
-        self.prev, _C1W_RECORDER = _C1W_RECORDER, self.queue
-        return self.queue
-
-    def __exit__(self, *exc):
-        global _C1W_RECORDER
-        _C1W_RECORDER = self.prev
-        return False
-
-
 def conv1d_wgrad_enabled():
     """S2SVC_NO_CONV1D_WGRAD=1 (read per call): today's launches everywhere."""
     return os.environ.get("S2SVC_NO_CONV1D_WGRAD", "0") != "1"
@@ -664,10 +624,10 @@ def conv1d_wgrad_supported(Cout, Cin, ks, dtype, bias=None):
 
 
 def conv1d_wgrad_queue(dy, x, dw):
-    """Queue dw += conv1d weight gradient of (dy, x) on the active recorder -> True; False (nothing done) without a recorder."""
-    if _C1W_RECORDER is None:
+    """Queue dw += conv1d weight gradient of (dy, x) on the active batch -> True; False (nothing done) without one."""
+    if _BATCH is None:
         return False
-    _C1W_RECORDER.append((dy, x, dw))
+    _BATCH.conv1d.append((dy, x, dw))
     return True
 
 
@@ -704,27 +664,11 @@ def conv1d_wgrad_grouped(items, cap=0):
     """dw[o][i][j] += sum_{b,t} dy[b,t,o] x[b,t+j-pad,i] for every (dy, x, dw) of `items`, on the current stream, in one launch of
     at most `cap` workgroups (0: one per unit) per <= 16 items; items on the same dw go to successive launches.  The library checks
     every item before the first launch and refuses what conv1d_wgrad_supported refuses."""
-    pending = [(_c1w_item(*t), t) for t in items]
-    while pending:
-        seen, group, rest = set(), [], []
-        for it, keep in pending:
-            if it.dw in seen:
-                rest.append((it, keep))
-            else:
-                seen.add(it.dw)
-                group.append((it, keep))
-        pending = rest
+    for group in disjoint_waves([(_c1w_item(*t), t) for t in items], lambda g: {g[0].dw}):
         arr = (_lib.Conv1dWgradItem * len(group))(*[g[0] for g in group])
         if _Audit.on:
             _audit_write("grouped conv1d weight gradient", *[g[0].dw for g in group])
         _lib.check(_lib.lib().s2svc_conv1d_wgrad_grouped(ctypes.addressof(arr), len(group), int(cap), stream()), "s2svc_conv1d_wgrad_grouped")
-
-
-def flush_conv1d_wgrad(queue, cap=0):
-    """Launch the queued conv1d weight gradients on the current stream (conv1d_wgrad_grouped).  Empties the queue."""
-    items = list(queue)
-    del queue[:]
-    conv1d_wgrad_grouped(items, cap)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -768,13 +712,13 @@ def layernorm_bwd(dy, s, mean, rstd, gamma, ds_extra=None, p=0.0, seed=(None, 0)
 def colreduce_partials(ws, chunks, D, out_sum, out_dot):
     """Second reduction stage for partial row pairs ws[chunks][2][D] that a producer kernel already wrote (layernorm_bwd with
     want_partials): out_sum / out_dot (fp32 gradient slots) += sum over the chunks.  Queued with the batch's grouped column
-    reductions when a recorder is active, else a grouped launch of its own."""
+    reductions when a batch is active, else a grouped launch of its own."""
     it = _lib.ColreduceItem()
     it.dy, it.x, it.mean, it.rstd = None, None, None, None
     it.out_sum, it.out_dot, it.ws = ptr(out_sum), ptr(out_dot), ptr(ws)
     it.dtype, it.rows, it.D, it.mode, it.accumulate, it.ws_chunks, it.scale = _DT[torch.float32], chunks, D, 7, 1, chunks, 1.0
-    if _CR_RECORDER is not None:
-        _CR_RECORDER.append((it, (out_sum, out_dot, ws)))
+    if _BATCH is not None:
+        _BATCH.colreduces.append((it, (out_sum, out_dot, ws)))
         return
     if _Audit.on:
         _audit_write("column reduction", ptr(out_sum), ptr(out_dot))
@@ -793,14 +737,14 @@ def colreduce(mode, dy, x=None, mean=None, rstd=None, scale=1.0, want_dot=False,
     t = dy if dy is not None else x
     D = t.shape[-1] if D is None else D
     rows = t.numel() // D if rows is None else rows
-    if _CR_RECORDER is not None and out_sum is not None and accumulate and vlens is None:
-        # parameter-gradient reduction into a flat-gradient slot: queued for the grouped launch (flush_colreduce)
+    if _BATCH is not None and out_sum is not None and accumulate and vlens is None:
+        # parameter-gradient reduction into a flat-gradient slot: queued for the grouped launch (GradBatch.flush)
         ws = torch.empty(_WS_CHUNKS * 2 * D, dtype=torch.float32, device=t.device)
         it = _lib.ColreduceItem()
         it.dy, it.x, it.mean, it.rstd = ptr(dy), ptr(x), ptr(mean), ptr(rstd)
         it.out_sum, it.out_dot, it.ws = ptr(out_sum), ptr(out_dot), ptr(ws)
         it.dtype, it.rows, it.D, it.mode, it.accumulate, it.ws_chunks, it.scale = dt(t), rows, D, mode, 1, _WS_CHUNKS, scale
-        _CR_RECORDER.append((it, (dy, x, mean, rstd, out_sum, out_dot, ws)))
+        _BATCH.colreduces.append((it, (dy, x, mean, rstd, out_sum, out_dot, ws)))
         return out_sum, out_dot
     if out_sum is None:
         out_sum = torch.empty(D, dtype=torch.float32, device=t.device)

@@ -14,6 +14,7 @@ from torch import nn
 
 from . import modules as Mo
 from .ops import functional as Fn
+from .ops import schedule as Sched
 from .ops import functional_aas as FA
 from .ops import functional_sdp as FS
 from .ops import kernels as K
@@ -204,8 +205,8 @@ class StochasticDurationPredictor(nn.Module):
         # stack, output projection, each -- are the last ~ 80 launches of this branch's backward pass and depend on nothing but the
         # gradients the flows accumulate in x and h_w: a stage plan may run them one stage later, beside the encoder's backward
         # pass (models/aas_vc.py: dp_plan).  Inactive (identity) outside distributed.OverlappedBackward.
-        x, h_w = Fn.cut_point((x, h_w), "sdp_cond")              # both networks one stage later
-        x = Fn.cut_point(x, "sdp_cond_x")                        # only the one behind x (the plan names ONE of the two cuts)
+        x, h_w = Sched.cut_point((x, h_w), "sdp_cond")              # both networks one stage later
+        x = Sched.cut_point(x, "sdp_cond_x")                        # only the one behind x (the plan names ONE of the two cuts)
         # tensors with several consumers go through Fn.fan_out: their gradients are summed by one launch of this library at ONE autograd
         # node instead of by the engine's element-wise adds (16 per step here: x 5 x, g_q 4 x, every flow's pass-through half 2 x)
         n_q = sum(isinstance(f, ConvFlow) for f in self.post_flows[1:])

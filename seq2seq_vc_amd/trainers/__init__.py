@@ -20,6 +20,7 @@ import torch
 from .. import distributed as D
 from ..optim import FlatAdam
 from ..ops import functional as Fn
+from ..ops import schedule as Sched
 from ..ops import kernels as K
 
 
@@ -116,7 +117,7 @@ class Trainer(object):
     def _schedule_gradient_work(self):
         if self.device.type == "cuda" and isinstance(self.optimizer, FlatAdam):
             n, inline = self.GRADIENT_WORK
-            Fn.enable_side_streams(self.config.get("side_streams", n), inline_batches=self.config.get("inline_batches", inline),
+            Sched.enable_side_streams(self.config.get("side_streams", n), inline_batches=self.config.get("inline_batches", inline),
                                    batch=self.config.get("gradient_batch", self.GRADIENT_BATCH))
 
     # -- data parallelism (reference: apex DistributedDataParallel wrap, bin/vc_train.py:423-431) ------------------------
@@ -171,13 +172,13 @@ class Trainer(object):
             fx = self.fx
             scale = 1.0 / self.world             # SUM exchange of gradients of loss / world == the mean the reference's DDP takes
             if not last_micro_step:              # an accumulation micro-step: no exchange
-                Fn.root_backward(total, scale)
-                Fn.side_join()
+                Sched.root_backward(total, scale)
+                Sched.side_join()
             elif not fx.select(self._graph_regime()):      # first step of this regime (eager): learn the plan while it runs
                 fx.learn_begin()
                 try:
-                    Fn.root_backward(total, scale)
-                    Fn.side_join()
+                    Sched.root_backward(total, scale)
+                    Sched.side_join()
                 finally:
                     fx.learn_end()
                 for h in D.allreduce_sum_begin(self.optimizer.flat_g, self.dist, self.world):
@@ -186,14 +187,14 @@ class Trainer(object):
                 self._capture.flush_backward(fx, total, scale)
             else:
                 with fx.recording():
-                    Fn.root_backward(total, scale)
-                    Fn.side_join()
+                    Sched.root_backward(total, scale)
+                    Sched.side_join()
                 fx.mark_end()
                 fx.issue()
                 fx.finish()
         else:
-            Fn.root_backward(total)
-            Fn.side_join()
+            Sched.root_backward(total)
+            Sched.side_join()
             if self.dist is not None and last_micro_step:
                 if isinstance(self.optimizer, FlatAdam):
                     D.allreduce_mean_(self.optimizer.flat_g, self.dist, self.world)
@@ -237,7 +238,7 @@ class Trainer(object):
             terms = []
             for k in self.loss_names:
                 v = losses[k]
-                v = v.detach() if isinstance(v, torch.Tensor) else Fn.const_scalar(self.device, float(v))
+                v = v.detach() if isinstance(v, torch.Tensor) else Sched.const_scalar(self.device, float(v))
                 if v.dtype != torch.float32 or not v.is_contiguous() or v.device != self.device:
                     v = v.to(device=self.device, dtype=torch.float32).contiguous()
                 terms.append((v, 1.0 / self.gradient_accumulate_steps))
@@ -418,7 +419,7 @@ class AASVCTrainer(Trainer):
             ret = self.model(xs, batch["ilens"], ys, batch["olens"], dp_inputs, dp_lengths=batch["dplens"])
             # loss = l1 + lambda_align * (forward_sum + bin) + duration (aas_vc.py:100-139): the sums -- and the division by the
             # accumulation steps (:141-143) -- are weights of ONE launch each way (Fn.weighted_sum), not a chain of 0-dim ATen ops
-            zero = Fn.const_scalar(dev, 0.0)
+            zero = Sched.const_scalar(dev, 0.0)
             lam, gas = float(self.config["lambda_align"]), float(self.gradient_accumulate_steps)
             logs = {}
             dec_terms = []

@@ -129,8 +129,8 @@ class GraphedStep:
         key = (name, tuple(st.shape), st.dtype)
         slot = self._stage.get(key)
         if self.copy_stream == "lazy":                 # (torch hands out stream objects round-robin: take one nothing else uses)
-            from ..ops import functional as Fn
-            self.copy_stream = Fn.distinct_stream(Fn._taken_streams() | {self.stream.cuda_stream})
+            from ..ops import schedule as Sched
+            self.copy_stream = Sched.distinct_stream(Sched.taken_streams() | {self.stream.cuda_stream})
         if slot is None:
             slot = self._stage[key] = {"buf": [torch.empty_like(st), torch.empty_like(st)], "free": [None, None], "i": 0}
             # the buffers were allocated on the step's stream: a block the caching allocator has just recycled may still be in
@@ -223,9 +223,9 @@ class GraphedStep:
         before = (t.steps, t.backward_steps)
         mode = "thread_local" if t.dist is not None else "global"
         torch.cuda.synchronize()
-        from ..ops import functional as Fn
-        if self.stream.cuda_stream in Fn._taken_streams():          # an alias out of torch's round-robin stream pool
-            self.stream = Fn.distinct_stream()
+        from ..ops import schedule as Sched
+        if self.stream.cuda_stream in Sched.taken_streams():          # an alias out of torch's round-robin stream pool
+            self.stream = Sched.distinct_stream()
         self.stream.wait_stream(torch.cuda.current_stream())
         cap = _Capture(self, e, mode)
         t._capture = cap if (t.dp is not None or getattr(t, "fx", None) is not None) else None
@@ -274,11 +274,9 @@ class _Capture:
 
     def end(self):
         g, stage = self.cur
-        from ..ops import functional as Fn
+        from ..ops import schedule as Sched
         main = torch.cuda.current_stream()
-        for st in [Fn._Branch.stream] + list(Fn._Side.streams):      # belt and braces: nothing may still be forked off
-            if st is None:
-                continue
+        for st in Sched.gradient_streams():      # belt and braces: nothing may still be forked off
             with torch.cuda.stream(st):
                 forked = torch.cuda.is_current_stream_capturing()
             if forked:
@@ -290,12 +288,12 @@ class _Capture:
     def flush_backward(self, fx, total, scale):
         """The uncut backward pass with a mark (an event-record node) behind every flushed gradient batch closes the first graph;
         what follows (the optimiser) is its own graph, replayed behind the exchange."""
-        from ..ops import functional as Fn
+        from ..ops import schedule as Sched
         self.cur = (self.cur[0], "fx")
         self.entry.fx_key = fx.key           # the plan (training regime) this graph's marks belong to
         with fx.recording():
-            Fn.root_backward(total, scale)
-            Fn.side_join()
+            Sched.root_backward(total, scale)
+            Sched.side_join()
         fx.mark_end()
         self.end()
         self.begin("opt")

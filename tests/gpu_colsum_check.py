@@ -159,14 +159,14 @@ def mode7_partials(chunks, D, exact, seed):
 
 @case
 def colreduce_grouped_exact():
-    """s2svc_colreduce_grouped through record_colreduce / flush_colreduce: 25 items (more than one launch holds), two items on one
+    """s2svc_colreduce_grouped through K.recording / GradBatch.flush: 25 items (more than one launch holds), two items on one
     output (successive launches), mode-7 items over hand-made partials."""
     t = Tally()
-    queue, want, keepalive = [], [], []
+    queue, want, keepalive = K.GradBatch(), [], []
     specs = [(mode, rows, D, dtype) for dtype in (F32, BF16) for (rows, D) in CS.COLREDUCE_SHAPES[1:5] for mode in (0, 1, 2)]
     specs.append((4, 300, 776, BF16))                                     # the 16-byte stage 1 inside the grouped kernel
     assert len(specs) == 25 and len(specs) > CS.CR_MAX
-    with K.record_colreduce(queue):
+    with K.recording(queue):
         for i, (mode, rows, D, dtype) in enumerate(specs):
             inp = CS.colreduce_inputs(mode, rows, D, dtype, exact=True, seed=i)
             t0, t1 = CS.colreduce_terms(mode, inp, F64)
@@ -192,8 +192,8 @@ def colreduce_grouped_exact():
             K.colreduce_partials(wsd, chunks, 72, osum.v, odot.v)
             want.append((f"grouped mode 7 chunks {chunks} sum", osum, prev[0] + ws[:, 0].to(F64).sum(0).to(F32)))
             want.append((f"grouped mode 7 chunks {chunks} dot", odot, prev[1] + ws[:, 1].to(F64).sum(0).to(F32)))
-    t.true("grouped", len(queue) == 25 + 2 + len(CS.MODE7_CHUNKS), f"{len(queue)} items queued")
-    K.flush_colreduce(queue)
+    t.true("grouped", len(queue.colreduces) == 25 + 2 + len(CS.MODE7_CHUNKS), f"{len(queue.colreduces)} items queued")
+    queue.flush()
     for tag, out, w in want:
         t.bits(tag, out.v, w)
         t.true(tag, out.tail_ok(), "wrote past D")

@@ -29,6 +29,7 @@ import conv1d_wgrad_ref as C  # noqa: E402
 import gpu_step_kernel_check as S  # noqa: E402  (Tally, sent, same_bits, refused: the idiom of the step-kernel check)
 from seq2seq_vc_amd import _lib  # noqa: E402
 from seq2seq_vc_amd.ops import functional as Fn  # noqa: E402
+from seq2seq_vc_amd.ops import schedule as Sched  # noqa: E402
 from seq2seq_vc_amd.ops import kernels as K  # noqa: E402
 
 DEV = "cuda"
@@ -234,7 +235,7 @@ def _postnet_run(off, x0, dy0):
         x = x0.clone().requires_grad_(True)
         y = net(x)
         y.backward(dy0)
-        Fn._side_flush()                 # the batch is forked HERE, capped (the one side_join flushes runs uncapped behind the chain)
+        Sched._side_flush()                 # the batch is forked HERE, capped (the one side_join flushes runs uncapped behind the chain)
         Fn.side_join()
         torch.cuda.synchronize()
     finally:

@@ -250,10 +250,10 @@ def test_four_rank_gloo_reduce_scatter_all_gather_equals_all_reduce():
 
 
 def test_gradient_cuts_split_the_backward_pass_without_changing_it():
-    """ops.functional.GradCuts (the stage boundaries of distributed.OverlappedBackward): a cut carrying ONE tensor and a cut
+    """ops.schedule.GradCuts (the stage boundaries of distributed.OverlappedBackward): a cut carrying ONE tensor and a cut
     carrying a TUPLE (residual stream + pending feed-forward output of a pre-norm layer stack, one member may be None) give the
     gradients of the uncut graph once every stage has been resumed; above a cut nothing below it has a gradient yet."""
-    from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import schedule as Fn
 
     torch.manual_seed(0)
     w = [torch.randn(6, 6, requires_grad=True) for _ in range(4)]
@@ -298,10 +298,10 @@ def test_gradient_cuts_split_the_backward_pass_without_changing_it():
 def test_branch_cut_with_shared_leaves_and_the_real_sdp_cut_points():
     """The round-4 stage plans cut INSIDE an auxiliary-stream branch: two conditioning networks feed many consumers (x feeds both
     flow stacks and, added to h_w, the posterior one), the cut carries (x, h_w) as a tuple, the flows' backward pass accumulates in
-    the detached leaves and a later stage resumes both networks in ONE autograd call (ops.functional.GradCuts; sdp.py: "sdp_cond" /
+    the detached leaves and a later stage resumes both networks in ONE autograd call (ops.schedule.GradCuts; sdp.py: "sdp_cond" /
     "sdp_cond_x"; distributed.OverlappedBackward with a cut as branch root).  CPU restatement of exactly that shape; and the model
     sources hold the cut points the plans name."""
-    from seq2seq_vc_amd.ops import functional as Fn
+    from seq2seq_vc_amd.ops import schedule as Fn
 
     torch.manual_seed(1)
     wa, wb = torch.randn(4, 4, requires_grad=True), torch.randn(4, 4, requires_grad=True)      # the two conditioning networks

@@ -172,12 +172,12 @@ def main():
         K._GROUP_MAX_TILES = 1 << 30
 
         def grouped():
-            q = []
-            with K.record_grouped(q):
+            q = K.GradBatch()
+            with K.recording(q):
                 for x, dy, dw, db in probs:
                     K.gemm(K.operand(dy, dy.shape[1], layout=K.RC), K.operand(x, x.shape[1], layout=K.RC), dy.shape[1], x.shape[1], 4096, dw,
                            in_dtype=dtype, accumulate=True, a_rowsum=db, a_rowsum_accumulate=True)
-            K.flush_grouped(q)
+            q.flush()
         for mode, nm in ((0, "4-wave"), (1 | (3 << 4), "8-wave 256x128"), (1 | (1 << 4), "8-wave 256x256"), (1, "8-wave policy")):
             L.s2svc_gemm_set_8ph(mode)
             us = bench(grouped, a.iters)
@@ -202,12 +202,12 @@ def main():
             gf = sum(2.0 * x.shape[0] * x.shape[1] * dy.shape[1] for x, dy, _, _ in probs)
 
             def grouped():
-                q = []
-                with K.record_grouped(q):
+                q = K.GradBatch()
+                with K.recording(q):
                     for x, dy, dw, db in probs:
                         K.gemm(K.operand(dy, dy.shape[1], layout=K.RC), K.operand(x, x.shape[1], layout=K.RC), dy.shape[1], x.shape[1], x.shape[0],
                                dw, in_dtype=dtype, accumulate=True, a_rowsum=db, a_rowsum_accumulate=True)
-                K.flush_grouped(q)
+                q.flush()
             for on, kt, nm in ((0, 0, "4-wave 64x64"), (1, 64, "W8 unsplit"), (1, 32, "W8 32-tile chunks"), (1, 16, "W8 16-tile chunks"), (1, 8, "W8 8-tile chunks")):
                 L.s2svc_gemm_set_w8(on, kt)
                 us = bench(grouped, a.iters)
